@@ -13,6 +13,14 @@ ships no dataset. One step = the reference's "Computation" phase (main.cu:301-40
 local group + F(U) + the global min-reduction (one RCCL all-reduce). TEPS counts, per group, the
 undirected edges of the components its sources reach (Graph500 convention), summed
 over all 1024 groups, divided by the step time. Total work is fixed as N grows: strong scaling.
+
+A plain run does only what the headline needs: preprocessing, one untimed edge-counting pass (the
+TEPS numerator), with several ranks the selection pass over the candidate decompositions, the
+warm-up and the K timed steps. --full adds the untimed extras: the cold step (cold_step_ms), the
+selection pass even when there is nothing to choose, the last timed step's F checked against the
+untimed pass, and --verify groups checked against the per-group distance solver.
+--dump-outputs DIR writes the last timed step's results (F.npy, argmin.npy; float64) for
+comparing two builds: graph and queries are seeded, so equal arguments give equal inputs.
 """
 from __future__ import annotations
 
@@ -78,9 +86,17 @@ def main() -> int:
     ap.add_argument("--algo", default="bitpar")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--qseed", type=int, default=7)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure (all untimed): the cold step, the "
+                         "selection pass even for a single decomposition, the timed F checked "
+                         "against the untimed pass, and --verify")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(float64): F (all groups, gathered over the ranks) and argmin "
+                         "(1-based minK, minF)")
     ap.add_argument("--verify", type=int, default=8,
-                    help="check this many groups (over all ranks) of the timed F against the "
-                         "per-group distance solver (untimed; 0 = off)")
+                    help="with --full: check this many groups (over all ranks) of the timed F "
+                         "against the per-group distance solver (untimed; 0 = off)")
     ap.add_argument("--alpha", type=float, default=0.0)
     ap.add_argument("--beta", type=float, default=0.0)
     ap.add_argument("--wide-degree", type=int, default=0)
@@ -215,22 +231,27 @@ def main() -> int:
             F[0] += 1
         return F, st
 
-    # cold step: the first computation after preprocessing (round robin, the reference's
-    # decomposition, with its blocking argmin; main.cu:301-400), reported next to the warm steps
     rr_idx = D.round_robin(qs.K, ctx.rank, ctx.world)
     rr_qs = qs.subset(rr_idx)
-    D.barrier(ctx)
-    sync()
-    t_cold = time.perf_counter()
-    D.packed_argmin(solver.run(rr_qs).F, rr_idx, qs.K, ctx)
-    sync()
-    cold_ms = D.allreduce_max(time.perf_counter() - t_cold, ctx) * 1e3
+    cold_ms = None
+    if args.full:
+        # cold step: the first computation after preprocessing (round robin, the reference's
+        # decomposition, with its blocking argmin; main.cu:301-400), reported next to the warm
+        # steps
+        D.barrier(ctx)
+        sync()
+        t_cold = time.perf_counter()
+        D.packed_argmin(solver.run(rr_qs).F, rr_idx, qs.K, ctx)
+        sync()
+        cold_ms = D.allreduce_max(time.perf_counter() - t_cold, ctx) * 1e3
     # untimed: TEPS numerator (traversed edges per group)
     r0 = solver.run(rr_qs, count_edges=True)
     total_edges = int(D.allreduce_sum_i64(np.array([int(r0.edges.sum())], np.int64), ctx)[0])
     # untimed: every candidate decomposition once (correctness check against the round-robin
-    # pass via the gathered F vector, and its time, max over ranks); the fastest one is timed
-    F_ref = D.gather_F(r0.F, rr_idx, qs.K, ctx)
+    # pass via the gathered F vector, and its time, max over ranks); the fastest one is timed.
+    # A plain run with a single candidate has nothing to choose and skips the pass.
+    select = args.full or len(candidates) > 1
+    F_ref = D.gather_F(r0.F, rr_idx, qs.K, ctx) if select or args.steps <= 0 else None
     # Each candidate runs twice and keeps its faster time: the first run of a decomposition can
     # carry one-time costs (e.g. RCCL setting up the all-to-all's peer connections) that would
     # otherwise decide the choice. Round robin goes first; a candidate that raises (on any rank)
@@ -241,17 +262,24 @@ def main() -> int:
         Fm, st = step(m, checked=True)
         return D.gather_F(Fm, plans[m][1], qs.K, ctx), st  # identical on every rank
 
-    cand_ms, errs = D.evaluate_candidates(candidates, run_gathered, F_ref, ctx,
-                                          reps=2 if ctx.distributed else 1,
-                                          sync=sync)
-    cand_err.update(errs)
-    for m, e in errs.items():
-        if ctx.rank == 0:
-            print(f"bench: candidate {m} excluded: {e}", file=sys.stderr)
-    if "roundrobin" in cand_err or not cand_ms:
-        print(f"rank {ctx.rank}: no verified decomposition: {cand_err}", file=sys.stderr)
+    cand_ms = {}
+    if select:
+        cand_ms, errs = D.evaluate_candidates(candidates, run_gathered, F_ref, ctx,
+                                              reps=2 if ctx.distributed else 1,
+                                              sync=sync)
+        cand_err.update(errs)
+        for m, e in errs.items():
+            if ctx.rank == 0:
+                print(f"bench: candidate {m} excluded: {e}", file=sys.stderr)
+        if "roundrobin" in cand_err or not cand_ms:
+            print(f"rank {ctx.rank}: no verified decomposition: {cand_err}", file=sys.stderr)
+            return 3
+        mode = min(cand_ms, key=cand_ms.get)
+    elif candidates:
+        mode = candidates[0]
+    else:
+        print(f"rank {ctx.rank}: no decomposition could be set up: {cand_err}", file=sys.stderr)
         return 3
-    mode = min(cand_ms, key=cand_ms.get)
     local_idx = plans[mode][1]
     # the step's global argmin: an async 8-byte MIN all-reduce, waited for once the next step's
     # BFS has run (the last one inside the timed region)
@@ -289,17 +317,31 @@ def main() -> int:
         xms = phases.get("exchange_ms") or 0.0
         phases["alltoall_GBps_per_rank"] = round(sent / (xms * 1e6), 1) if xms > 0 else None
         phases["chunks"] = int(stats.get("chunks", 1))  # exchange pieces overlapped with phase A
-    # ---- untimed self-check of the timed result: the last timed step's F (all ranks, gathered)
-    # equals the untimed pass, and the first groups of every rank equal the per-group distance
-    # solver's F (an independent algorithm: one int32 distance per vertex, main.cu:40-89)
-    F_last = D.gather_F(F, local_idx, qs.K, ctx) if args.steps > 0 else F_ref
-    if not np.array_equal(F_last, F_ref):
+    # the last timed step's F of all ranks, gathered (without timed steps: the untimed pass's)
+    F_last = None
+    if args.steps <= 0:
+        F_last = F_ref
+        k = msbfs.argmin_first(F_ref)
+        min_k, min_f = k, (int(F_ref[k]) if k >= 0 else -1)
+    elif args.full or args.dump_outputs:
+        F_last = D.gather_F(F, local_idx, qs.K, ctx)
+    if args.dump_outputs and ctx.rank == 0:
+        # what a caller of the timed path receives: F of every group and the argmin (1-based
+        # minK as the report prints it); F < 2^53, so float64 holds it exactly
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "F.npy"), np.asarray(F_last, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "argmin.npy"),
+                np.array([int(min_k) + 1, int(min_f)], dtype=np.float64))
+    # ---- --full: untimed self-check of the timed result: the last timed step's F equals the
+    # untimed pass, and the first groups of every rank equal the per-group distance solver's F
+    # (an independent algorithm: one int32 distance per vertex, main.cu:40-89)
+    if args.full and not np.array_equal(F_last, F_ref):
         bad = np.flatnonzero(F_last != F_ref)[:8]
         print(f"rank {ctx.rank}: timed F differs from the untimed pass at groups {bad}",
               file=sys.stderr)
         return 3
     verified, verify_err = 0, ""
-    if args.verify > 0:
+    if args.full and args.verify > 0:
         nv = min(len(rr_idx), -(-args.verify // ctx.world))
         ok = 1.0
         if nv:
@@ -316,9 +358,6 @@ def main() -> int:
         if D.allreduce_max(1.0 - ok, ctx) > 0:
             return 3
         verified = int(D.allreduce_sum_i64(np.array([nv], np.int64), ctx)[0])
-    if args.steps == 0:
-        k = msbfs.argmin_first(F_ref)
-        min_k, min_f = k, (int(F_ref[k]) if k >= 0 else -1)
     value = total_edges / (ms / 1e3) if ms > 0 else 0.0
     if ctx.rank == 0:
         out = {
@@ -351,12 +390,13 @@ def main() -> int:
                 "dirs": "".join(t["dir"] for t in trace),
                 "level_ms": [round(t["ms"], 3) for t in trace],
                 "setup_s": round(setup_s, 3), "relabel": relabelled,
-                "cold_step_ms": round(cold_ms, 3),
+                "full": args.full,
+                **({"cold_step_ms": round(cold_ms, 3)} if cold_ms is not None else {}),
                 "candidates_ms": {k: round(v, 3) for k, v in cand_ms.items()},
                 "candidate_errors": cand_err,
                 "devices": devices, "process_group_size": pg_size, "backend": ctx.backend,
                 **({"phases": phases} if phases else {}),
-                "timed_F_equals_untimed": True,
+                **({"timed_F_equals_untimed": True} if args.full else {}),
                 "verified_groups_vs_dist_solver": verified,
                 **({"verify_skipped": verify_err} if verify_err else {}),
             },

@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +30,7 @@ def test_bench_forced_rccl_one_rank(dist):
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "18",
                         "--groups", "300", "--steps", "2", "--warmup", "1", "--dist", dist,
-                        "--verify", "8"],
+                        "--full", "--verify", "8"],
                        capture_output=True, text=True, env=env, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     js = json.loads(r.stdout.strip().splitlines()[-1])
@@ -89,7 +90,7 @@ def test_bench_multi_rank_gloo_shared_gpu(ranks, dist):
                         "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
                         "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus",
                         str(ranks), "--scale", "16", "--groups", "200", "--steps", "2", "--warmup", "1", "--dist", dist,
-                        "--backend", "gloo", "--verify", "4"],
+                        "--backend", "gloo", "--full", "--verify", "4"],
                        capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     js = json.loads(r.stdout.strip().splitlines()[-1])
@@ -123,7 +124,7 @@ def test_bench_two_ranks_rccl(dist):
         pytest.skip("needs two GPUs (one per RCCL rank)")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale",
                         "18", "--groups", "300", "--steps", "2", "--warmup", "1", "--dist", dist,
-                        "--verify", "4"],
+                        "--full", "--verify", "4"],
                        capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     js = json.loads(r.stdout.strip().splitlines()[-1])
@@ -149,7 +150,7 @@ def test_bench_falls_back_when_a_candidate_kills_the_run(fault, dist, expect):
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus",
                         "2", "--scale", "14", "--groups", "200", "--steps", "2", "--warmup", "1",
-                        "--backend", "gloo", "--verify", "4", "--dist", dist],
+                        "--backend", "gloo", "--full", "--verify", "4", "--dist", dist],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -171,7 +172,7 @@ def test_bench_excludes_wrong_candidate(bad):
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus",
                         "2", "--scale", "16", "--groups", "200", "--steps", "2", "--warmup", "1",
-                        "--backend", "gloo", "--verify", "4", "--test-corrupt", bad],
+                        "--backend", "gloo", "--full", "--verify", "4", "--test-corrupt", bad],
                        capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     js = json.loads(r.stdout.strip().splitlines()[-1])
@@ -188,7 +189,7 @@ def test_bench_wrong_roundrobin_fails():
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus",
                         "2", "--scale", "14", "--groups", "100", "--steps", "1", "--warmup", "0",
-                        "--backend", "gloo", "--test-corrupt", "roundrobin"],
+                        "--backend", "gloo", "--full", "--test-corrupt", "roundrobin"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -203,7 +204,8 @@ def test_bench_without_rccl_falls_back_to_gloo():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale",
-                        "14", "--groups", "100", "--steps", "2", "--warmup", "1", "--verify", "4"],
+                        "14", "--groups", "100", "--steps", "2", "--warmup", "1", "--full",
+                        "--verify", "4"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -223,7 +225,7 @@ def test_bench_gpus_flag_launches_ranks():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
                         "--backend", "gloo", "--scale", "16", "--groups", "200", "--steps", "2",
-                        "--warmup", "1", "--verify", "8"],
+                        "--warmup", "1", "--full", "--verify", "8"],
                        capture_output=True, text=True, timeout=110, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     js = json.loads(r.stdout.strip().splitlines()[-1])
@@ -232,11 +234,44 @@ def test_bench_gpus_flag_launches_ranks():
 
 
 def test_bench_one_gpu_self_verifies():
-    """The default headline run checks itself: verified >= 8 groups against the distance solver
-    (untimed) and the last timed step's F equal to the untimed pass."""
+    """The headline run with --full checks itself: verified >= 8 groups against the distance
+    solver (untimed) and the last timed step's F equal to the untimed pass."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "18",
-                        "--groups", "256", "--steps", "2", "--warmup", "1"],
+                        "--groups", "256", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     js = json.loads(r.stdout.strip().splitlines()[-1])
     assert js["verified"] >= 8 and js["n_gpus"] == 1
+    assert js["config"]["full"] and js["config"]["cold_step_ms"] > 0
+    assert js["config"]["timed_F_equals_untimed"] and "roundrobin" in js["config"]["candidates_ms"]
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(msbfs_pkg, tmp_path):
+    """A plain run (no --full) times its steps without the cold step, the selection pass or the
+    self-checks, and --dump-outputs writes the last timed step's F and argmin as float64 .npy:
+    equal from run to run (seeded inputs) and equal to the CPU oracle's."""
+    msbfs = msbfs_pkg
+    outs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                            "--scale", "14", "--groups", "130", "--group-size", "3", "--steps",
+                            "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=110, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        js = json.loads(r.stdout.strip().splitlines()[-1])
+        assert js["steps"] == 3 and js["ms_per_step"] > 0 and js["value"] > 0
+        assert js["verified"] == 0 and not js["config"]["full"]
+        assert js["config"]["candidates_ms"] == {} and "cold_step_ms" not in js["config"]
+        assert "timed_F_equals_untimed" not in js["config"]
+        assert sorted(os.listdir(tmp_path / d)) == ["F.npy", "argmin.npy"]
+        outs.append((np.load(tmp_path / d / "F.npy"), np.load(tmp_path / d / "argmin.npy"), js))
+    (Fa, am_a, js), (Fb, am_b, _) = outs
+    assert Fa.dtype == np.float64 and Fa.shape == (130,) and am_a.dtype == np.float64
+    assert np.array_equal(Fa, Fb) and np.array_equal(am_a, am_b)
+    g = msbfs.Graph.rmat(14, 16, 1)
+    ref = msbfs.cpu_bfs(g, msbfs.QuerySet.random(g.n, 130, 3, 7), count_edges=True)
+    k = msbfs.argmin_first(ref.F)
+    assert np.array_equal(Fa, ref.F.astype(np.float64))
+    assert am_a.tolist() == [k + 1, int(ref.F[k])]
+    assert js["config"]["traversed_edges"] == int(ref.edges.sum())
+    assert js["config"]["min_k"] == k + 1 and js["config"]["min_f"] == int(ref.F[k])

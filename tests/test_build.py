@@ -42,6 +42,16 @@ def test_bench_rejects_world_size_mismatch():
     assert r.returncode == 2 and "WORLD_SIZE=3" in r.stderr
 
 
+def test_bench_options_present():
+    """bench.py offers --full (the untimed extras) and --dump-outputs DIR next to the driver's
+    --gpus/--steps/--warmup (parsed before anything touches the GPU)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
+                       capture_output=True, text=True, timeout=60, cwd=ROOT)
+    assert r.returncode == 0, r.stderr
+    for opt in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs DIR"):
+        assert opt in r.stdout, opt
+
+
 def test_level_record_layout(tmp_path):
     """The ctypes mirrors of the C API's structs (msbfs_level, msbfs_stats, msbfs_options in
     msbfs.h) have the C compiler's size and field offsets: the per-level records, run stats and

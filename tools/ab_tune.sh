@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of tuning settings on the GPU box: for each "label=spec" run bench.py (MSBFS_TUNE=spec,
 # "-" for the defaults) and print ms/step and the per-level ms; stops at the first failure.
-#   bash tools/ab_tune.sh "base=-" "e1=exp=1" -- --steps 10 --warmup 3 --verify 4
+#   bash tools/ab_tune.sh "base=-" "e1=exp=1" -- --steps 10 --warmup 3 --full --verify 4
 set -u
 mkdir -p gpurun_out
 specs=()

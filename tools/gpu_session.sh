@@ -33,7 +33,7 @@ for s in "$@"; do
     pytest_kernels) step pytest_kernels 900 $PT tests/test_gpu_kernels.py -m gpu ;;
     pytest_rest) step pytest_rest 900 $PT tests -m gpu --deselect tests/test_gpu_kernels.py ;;
     smoke) step smoke 300 python __graft_entry__.py smoke ;;
-    bench26) step bench26 300 python bench.py --steps 20 --warmup 5 ;;
+    bench26) step bench26 300 python bench.py --steps 20 --warmup 5 --full ;;
     bench2r) step bench2r 600 python bench.py --gpus 2 --backend gloo --scale 22 --steps 2 --warmup 1 ;;
     trace26) MSBFS_TRACE=1 step trace26 300 python bench.py --steps 2 --warmup 1 ;;
     trace128) MSBFS_TRACE=1 step trace128 300 python bench.py --steps 2 --warmup 1 --groups 128 ;;
@@ -43,7 +43,7 @@ for s in "$@"; do
     prof512) prof prof512 600 python bench.py --groups 512 --steps 1 --warmup 0 --verify 0 ;;
     prof30) prof prof30 900 python bench.py --scale 30 --groups 32 --steps 1 --warmup 1 --verify 0 ;;
     prof22) prof prof22 300 python bench.py --scale 22 --groups 64 --steps 3 --warmup 1 --verify 0 ;;
-    rmat22) step rmat22 300 python bench.py --scale 22 --groups 64 --steps 5 --warmup 1 --verify 16 ;;
+    rmat22) step rmat22 300 python bench.py --scale 22 --groups 64 --steps 5 --warmup 1 --full --verify 16 ;;
     rmat30) MSBFS_TRACE=1 step rmat30 1000 python bench.py --scale 30 --groups 256 --steps 1 --warmup 0 ;;
     road) step road 900 python tools/bench_graph.py --graph grid:4896:4896:0.6 --groups 64 --steps 1 --verify 2 ;;
     road16) step road16 900 python tools/bench_graph.py --graph grid:4896:4896:0.6 --groups 16 --steps 1 ;;
