@@ -75,8 +75,9 @@ struct DeviceGraph {
   DevBuf own_rowptr, own_col;
   int64_t max_degree = 0;
   int64_t isolated = 0;
-  // Optional degree-descending relabelling: old2new[v] maps a user vertex id to the internal id
-  // (null when the graph keeps the user's ids). Solvers map query sources through it.
+  // Optional relabelling (degree descending, see device_graph_relabel_by_degree): old2new[v] maps
+  // a user vertex id to the internal id (null when the graph keeps the user's ids). Solvers map
+  // query sources through it.
   int32_t* old2new = nullptr;
   DevBuf own_old2new;
   // every row's neighbour ids ascending (device_graph_sort_rows; relabelling sorts too). Solvers
@@ -114,8 +115,13 @@ void device_graph_gen_rmat(DeviceGraph& g, int scale, int64_t edgefactor, uint64
 void device_graph_gen_uniform(DeviceGraph& g, int64_t n, int64_t m, uint64_t seed, hipStream_t s);
 void device_graph_stats(DeviceGraph& g, hipStream_t s);
 void device_graph_sort_rows(DeviceGraph& g, hipStream_t s);
-// Renumber vertices by descending degree (stable), rebuild the CSR with sorted rows and keep the
-// old->new map in g.old2new. F(U) is invariant under relabelling.
+// Renumber vertices by descending degree, rebuild the CSR with sorted rows and keep the old->new
+// map in g.old2new. F(U) is invariant under relabelling. Vertices of equal degree keep their id
+// order, except on skewed graphs (max degree > 16 x the mean): there they are ordered by the new
+// id of their highest-degree neighbour first, then by old id, so that consecutive vertices
+// gather the same hub rows. MSBFS_RELABEL_LOCALITY=0|1 forces that key off or on; without room
+// for its buffers the id order stays (one line on stderr). Otherwise the order is a function of
+// the graph alone: ranks with the same setting number vertices alike.
 void device_graph_relabel_by_degree(DeviceGraph& g, hipStream_t s);
 
 // ---- solvers ---------------------------------------------------------------------------------

@@ -98,7 +98,9 @@ int msbfs_graph_gen_uniform(int device, int64_t n, int64_t m, uint64_t seed, msb
 int msbfs_graph_from_edge_file(int device, const char* path, msbfs_graph* out);
 int msbfs_graph_sort_rows(msbfs_graph g);
 /* Renumber vertices by descending degree (hubs first, rows sorted). Queries keep using the
- * original ids: solvers map sources through the stored old->new map. */
+ * original ids: solvers map sources through the stored old->new map. On skewed graphs vertices
+ * of equal degree are ordered by their highest-degree neighbour (MSBFS_RELABEL_LOCALITY=0|1
+ * forces that off or on), otherwise by id. */
 int msbfs_graph_relabel_by_degree(msbfs_graph g);
 int msbfs_graph_relabel_map(msbfs_graph g, int32_t* old2new);
 int msbfs_graph_is_relabelled(msbfs_graph g);

@@ -406,7 +406,7 @@ __global__ __launch_bounds__(kBlock) void k_invert_perm(const int32_t* perm, int
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     old2new[perm[i]] = (int32_t)i;
-    newdeg[i] = (int64_t)sdeg[i];
+    if (newdeg) newdeg[i] = (int64_t)sdeg[i];
   }
 }
 // one wave per new row: copy the old row of perm[i], mapping every neighbour through old2new
@@ -423,11 +423,93 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(const int64_t* orow, con
     for (int64_t j = lane; j < len; j += 64) ncol[nb + j] = old2new[ocol[b + j]];
   }
 }
+
+// Locality key of the relabelling: key2[v] = min over v's neighbours u of prov[u], the id of its
+// highest-degree neighbour in the degree-only order (UINT32_MAX for an isolated vertex). A group
+// of kKeyLanes lanes takes one row; rows longer than kKeyShort are left to k_min_nbr_long.
+constexpr int kKeyLanes = 8, kKeyShort = 256;
+__global__ __launch_bounds__(kBlock) void k_min_nbr_short(const int64_t* rowptr, const int32_t* col,
+                                                          const int32_t* prov, int64_t n,
+                                                          uint32_t* key2) {
+  const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kKeyLanes;
+  const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) / kKeyLanes;
+  const int sub = (int)(threadIdx.x % kKeyLanes);
+  const int64_t lim = (n + ngrp - 1) / ngrp * ngrp;  // whole waves reach the shuffles
+  for (int64_t v = grp; v < lim; v += ngrp) {
+    int64_t b = 0, len = kKeyShort + 1;
+    if (v < n) {
+      b = rowptr[v];
+      len = rowptr[v + 1] - b;
+    }
+    uint32_t mn = UINT32_MAX;
+    if (len <= kKeyShort)
+      for (int64_t j = sub; j < len; j += kKeyLanes) mn = min(mn, (uint32_t)prov[col[b + j]]);
+    for (int off = kKeyLanes / 2; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off));
+    if (sub == 0 && len <= kKeyShort) key2[v] = mn;
+  }
+}
+// one block per long row (hubs: up to millions of neighbours)
+__global__ __launch_bounds__(kBlock) void k_min_nbr_long(const int64_t* rowptr, const int32_t* col,
+                                                         const int32_t* prov, int64_t n,
+                                                         uint32_t* key2) {
+  __shared__ uint32_t part[kBlock / 64];
+  for (int64_t v = blockIdx.x; v < n; v += gridDim.x) {
+    const int64_t b = rowptr[v], len = rowptr[v + 1] - b;
+    if (len <= kKeyShort) continue;  // (block-uniform)
+    uint32_t mn = UINT32_MAX;
+    for (int64_t j = threadIdx.x; j < len; j += kBlock) mn = min(mn, (uint32_t)prov[col[b + j]]);
+    for (int off = 32; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off));
+    if (lane_id() == 0) part[threadIdx.x >> 6] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 1; w < kBlock / 64; ++w) mn = min(mn, part[w]);
+      key2[v] = mn;
+    }
+    __syncthreads();
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_gather_u32(const uint32_t* src, const int32_t* idx,
+                                                       int64_t n, uint32_t* dst) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    dst[i] = src[idx[i]];
+}
+
+// stable radix sort of (key, value) pairs by the whole 32-bit key
+void sort_pairs_u32(bool descending, const uint32_t* kin, uint32_t* kout, const int32_t* vin,
+                    int32_t* vout, int64_t n, hipStream_t s) {
+  size_t tb = 0;
+  DevBuf temp;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass) temp.alloc(tb);
+    if (descending)
+      MSBFS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairsDescending(temp.p, tb, kin, kout, vin,
+                                                                   vout, (int)n, 0, 32, s));
+    else
+      MSBFS_HIP_CHECK(
+          hipcub::DeviceRadixSort::SortPairs(temp.p, tb, kin, kout, vin, vout, (int)n, 0, 32, s));
+  }
+  MSBFS_HIP_CHECK(hipStreamSynchronize(s));  // temp is freed on return
+}
+
+// Whether equal-degree vertices are ordered by their top hub: MSBFS_RELABEL_LOCALITY=0|1 decides;
+// otherwise only skewed graphs are (max degree > 16 x the mean over the non-isolated vertices,
+// the test Solver::gamma_for uses): on a grid or a uniform graph the id order within a degree
+// class is all the locality there is.
+bool relabel_locality_wanted(const DeviceGraph& g) {
+  if (const char* e = getenv("MSBFS_RELABEL_LOCALITY"))
+    if (*e) return atoi(e) != 0;
+  const double mean = (double)g.nnz / (double)std::max<int64_t>(g.n - g.isolated, 1);
+  return (double)g.max_degree > 16.0 * mean;
+}
 }  // namespace
 
 void device_graph_relabel_by_degree(DeviceGraph& g, hipStream_t s) {
   const int64_t n = g.n;
   if (n == 0 || g.old2new) return;
+  // Order: degree descending; on skewed graphs (relabel_locality_wanted) equal-degree vertices
+  // then go by the rank of their highest-degree neighbour, so that consecutive vertices gather
+  // the same hub rows in the pull levels; last by old id.
   // The rebuild holds a second column array next to the first. A device-generated graph without
   // room for it (RMAT-30: 128 GiB of columns) is regenerated in the new ids instead: same rows,
   // and after the row sort the same CSR. MSBFS_RELABEL_REGEN=1 forces that path (tests).
@@ -442,24 +524,59 @@ void device_graph_relabel_by_degree(DeviceGraph& g, hipStream_t s) {
       fail("not enough device memory to relabel the graph (needs a second " +
            std::to_string(g.nnz * 4 >> 20) + " MiB column array)");
   }
-  DevBuf deg(n * 4), sdeg(n * 4), ids(n * 4), perm(n * 4), newdeg(n * 8);
+  DevBuf deg(n * 4), sdeg(n * 4), ids(n * 4), perm(n * 4);
   k_deg_iota<<<grid_for(n, kBlock), kBlock, 0, s>>>(g.rowptr, n, deg.as<uint32_t>(),
                                                     ids.as<int32_t>());
   MSBFS_HIP_CHECK(hipGetLastError());
-  size_t tb = 0;
-  MSBFS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairsDescending(
-      nullptr, tb, deg.as<uint32_t>(), sdeg.as<uint32_t>(), ids.as<int32_t>(), perm.as<int32_t>(),
-      (int)n, 0, 32, s));
-  {
-    DevBuf temp(tb);
-    MSBFS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairsDescending(
-        temp.p, tb, deg.as<uint32_t>(), sdeg.as<uint32_t>(), ids.as<int32_t>(),
-        perm.as<int32_t>(), (int)n, 0, 32, s));
+  // degree descending, ties by old id (the sort is stable): the final order, or the provisional
+  // one that the locality key is taken from
+  sort_pairs_u32(true, deg.as<uint32_t>(), sdeg.as<uint32_t>(), ids.as<int32_t>(),
+                 perm.as<int32_t>(), n, s);
+  bool locality = relabel_locality_wanted(g);
+  if (locality) {
+    // two more id-sized buffers (the key, and the map before deg and ids are gone) next to a
+    // second sort's temporary storage, taken to be no larger than the pairs it sorts
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
+        (double)free_b < (double)n * 16.0 + (double)(size_t(256) << 20)) {
+      static bool said = false;
+      if (!said)
+        fprintf(stderr, "msbfs: no device memory for the relabelling's locality key: equal-degree "
+                        "vertices keep their id order\n");
+      said = true;
+      locality = false;
+    }
+  }
+  g.own_old2new.alloc(n * 4);
+  int32_t* o2n = g.own_old2new.as<int32_t>();
+  if (locality) {
+    // Final order (degree descending, key2 ascending, old id ascending) by two stable passes:
+    // by key2, then by degree. key2 reads the original CSR, so the gather and the regeneration
+    // path below see the same keys. Hubs have near-unique degrees and keep their ranks.
+    DevBuf key2(n * 4);
+    k_invert_perm<<<grid_for(n, kBlock), kBlock, 0, s>>>(perm.as<int32_t>(), n, o2n, nullptr,
+                                                         nullptr);
+    MSBFS_HIP_CHECK(hipGetLastError());
+    k_min_nbr_short<<<grid_for(n * kKeyLanes, kBlock, 8192), kBlock, 0, s>>>(
+        g.rowptr, g.col, o2n, n, key2.as<uint32_t>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+    if (g.max_degree > kKeyShort) {
+      k_min_nbr_long<<<grid_for(n, 1, 8192), kBlock, 0, s>>>(g.rowptr, g.col, o2n, n,
+                                                            key2.as<uint32_t>());
+      MSBFS_HIP_CHECK(hipGetLastError());
+    }
+    sort_pairs_u32(false, key2.as<uint32_t>(), sdeg.as<uint32_t>(), ids.as<int32_t>(),
+                   perm.as<int32_t>(), n, s);
+    k_gather_u32<<<grid_for(n, kBlock), kBlock, 0, s>>>(deg.as<uint32_t>(), perm.as<int32_t>(), n,
+                                                        key2.as<uint32_t>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+    sort_pairs_u32(true, key2.as<uint32_t>(), sdeg.as<uint32_t>(), perm.as<int32_t>(),
+                   ids.as<int32_t>(), n, s);
+    std::swap(perm, ids);
   }
   deg.release();
   ids.release();
-  g.own_old2new.alloc(n * 4);
-  int32_t* o2n = g.own_old2new.as<int32_t>();
+  DevBuf newdeg(n * 8);
   k_invert_perm<<<grid_for(n, kBlock), kBlock, 0, s>>>(perm.as<int32_t>(), n, o2n,
                                                        sdeg.as<uint32_t>(), newdeg.as<int64_t>());
   MSBFS_HIP_CHECK(hipGetLastError());

@@ -208,7 +208,9 @@ class DeviceGraph:
     def relabel_by_degree(self) -> "DeviceGraph":
         """Renumber vertices by descending degree (hubs first, sorted rows) in place. Queries
         keep using the original ids — solvers map sources through the stored map; F(U) is
-        label-invariant. download() then returns the relabelled CSR."""
+        label-invariant. download() then returns the relabelled CSR. On skewed graphs vertices
+        of equal degree are ordered by their highest-degree neighbour, otherwise by id
+        (MSBFS_RELABEL_LOCALITY=0|1 forces that off or on)."""
         native.check(native.lib().msbfs_graph_relabel_by_degree(self.handle))
         self._refresh()
         return self
