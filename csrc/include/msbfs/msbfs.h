@@ -36,11 +36,13 @@ typedef struct {
 } msbfs_stats;
 
 /* one BFS level of the last run (bit-parallel solver): direction 'T' (top-down push) or 'B'
- * (bottom-up pull), union frontier size / degree sum entering the level, vertices newly visited
+ * (bottom-up pull), kind of a pull level's narrow-list pull ('t' tiles, 'p' per-vertex prefix,
+ * 'h' LDS-hub filtered, 'l' lean + overflow, 'f' full, 'n' plain narrow; 0 for push levels),
+ * union frontier size / degree sum entering the level, vertices newly visited
  * by some group, bottom-up active (or top-down touched) vertices, host wall time of the level */
 typedef struct {
   int32_t batch, level;
-  char dir, pad[3];
+  char dir, kind, pad[2];
   int64_t nf, ef, nf_next, active;
   double ms;
 } msbfs_level;

@@ -7,7 +7,7 @@
 //     timeline next to the kernels. Compiled in when the rocprofiler-sdk roctx library is present
 //     (MSBFS_HAVE_ROCTX), otherwise the calls are empty inlines. MSBFS_ROCTX=0 disables them at
 //     run time.
-//   * LevelRec: one record per BFS level (direction, frontier / active sizes, host wall time of
+//   * LevelRec: one record per BFS level (direction, pull kind, frontier / active sizes, host wall time of
 //     the level including its counter read-back), kept in RunStats and exported through the C API
 //     (msbfs_solver_levels) and the CLI's --json line.
 #pragma once
@@ -20,6 +20,10 @@ struct LevelRec {
   int32_t batch = 0;       // batch index (groups beyond one pass run as further batches)
   int32_t level = 0;       // BFS level (1 = first expansion from the sources)
   char dir = 'T';          // 'T' top-down (push) or 'B' bottom-up (pull)
+  // pull levels: the narrow-list pull the level's plan chose (bp::PullKind: 't' tiles, 'p'
+  // per-vertex prefix, 'h' LDS-hub filtered, 'l' lean + overflow, 'f' full, 'n' plain narrow;
+  // device-driven pull batches 'f' or 'n'); push levels 0
+  char kind = 0;
   int64_t nf = 0;          // union frontier entering the level (vertices)
   int64_t ef = 0;          // its degree sum
   int64_t nf_next = 0;     // vertices newly visited by some group at this level

@@ -519,7 +519,8 @@ int64_t msbfs_solver_levels(msbfs_solver s, msbfs_level* out, int64_t cap) {
   const int64_t n = (int64_t)s->recs.size();
   for (int64_t i = 0; out && i < std::min(n, cap); ++i) {
     const msbfs::LevelRec& r = s->recs[i];
-    out[i] = msbfs_level{r.batch, r.level, r.dir, {0, 0, 0}, r.nf, r.ef, r.nf_next, r.active, r.ms};
+    out[i] = msbfs_level{r.batch, r.level,   r.dir,    r.kind,   {0, 0},
+                         r.nf,    r.ef,      r.nf_next, r.active, r.ms};
   }
   return n;
 }

@@ -29,11 +29,14 @@
 // spread over G = W/VW consecutive lanes, so W=16 reads a vertex's 128-B line in one coalesced
 // wave-instruction slice.
 //
-// Source layout (one class, four translation units that compile in parallel):
+// Source layout (one class, five translation units that compile in parallel):
 //   bitpar/common.hpp  init.hpp  push.hpp  pull.hpp  hybrid.hpp   kernels by family
 //   bitpar_solver.hip  construction, batches, the level loop (direction choice, reductions)
 //   bitpar_push.hip    top-down levels and the device-driven level batches
-//   bitpar_pull.hip    bottom-up levels (prefix pull + tail push, narrow / lean / chunk pulls)
+//   bitpar_pull.hip    bottom-up levels (prefix pull + tail push, narrow / lean / chunk pulls),
+//                      each carried out from a plan: bitpar/pull_plan.hpp (plain host code)
+//   bitpar_tiles.hip   the first pull level over static vertex tiles
+//   bitpar/tuning.hpp, ../bitpar_tuning.cpp   the tuning keys and their parser (plain host code)
 //   bitpar_hybrid.hip  the hybrid multi-GPU phases and the exchange coding
 #pragma once
 
@@ -44,84 +47,10 @@
 #include <string>
 
 #include "common.hpp"
+#include "pull_plan.hpp"
 
 namespace msbfs {
 namespace bp {
-
-// Algorithm tuning of the bit-parallel solver. Defaults are the measured best (RMAT-26 / 1024
-// groups, RMAT-30, road grid, uniform graphs; see README). Set per solver through
-// Solver::tune ("key=value,key=value"; msbfs_solver_tune in the C API, Solver(tuning=...) in
-// Python) or process-wide through the one variable MSBFS_TUNE (same syntax; echoed on stderr).
-// Unknown keys and malformed values are errors, never ignored. Every key is exercised by a GPU
-// oracle test (tests/test_gpu_kernels.py).
-struct Tuning {
-  // push -> pull once the frontier's degree sum exceeds gamma x n_eff (0: off). Level 2, where
-  // the prefix pull applies, uses gamma2 (< 0: gamma): RMAT-30 / 16 groups 296 -> 106 ms
-  double gamma = 1.0, gamma2 = 0.25;
-  bool gamma2_auto = true;  // gamma2 not set explicitly: only skewed graphs use it (gamma_for)
-  // first bottom-up level: 0 = whole-row pull; 2 = prefix pull (ids < 458752, the 56-KB LDS hub
-  // bitmap) + tail push (RMAT-26 level 2: 16.8 ms vs 21.2 for whole rows)
-  int pfx = 2;
-  // sparse single-group row codes on the first bottom-up level; ids with degree >=
-  // code_deg * nnz / (source degree sum), i.e. >= code_deg expected set bits, keep row gathers
-  int codes = 1;
-  double code_deg = 3.0;
-  // lean first-row pass on the third and later pull levels (k_bu_first) for active lists of at
-  // least lean_min vertices (RMAT-26 level 4: 2.48 -> 2.07 ms)
-  int lean = 1;
-  int64_t lean_min = 1 << 20;
-  int lazy = 1;        // no per-batch fill of the visited buffer (see start_batch)
-  int td_fused = 1;    // device-driven batches run the one-kernel k_td_fused levels
-  // k_td_fused walks the frontier bitmap from this frontier size on (road grid 4896^2, two
-  // sessions: 64 groups 306.8-307.2 -> 302.9-304.3 ms, 16 groups 142.8 -> 139.4, 256 groups
-  // 1377 -> 1370 against 65536; 32768 ran 310, 262144 305 ms at 64 groups)
-  int64_t td_bm = 131072;
-  int batch = 64;      // top-down levels per device-driven batch (1 = host-driven levels)
-  // pull levels from the third on run as device-driven batches (bu_batch) while the active lists
-  // hold at most bu_max vertices (0 = host-driven pull levels; needs batch > 1)
-  int64_t bu_max = 1 << 20;
-  int tiles = 1;       // first pull level over static vertex tiles (bitpar/tiles.hpp)
-  int tiles_w = 8;     // fewest words per vertex that take the tiled first pull level (4, 8 or 16)
-  // unfiltered pull levels (the second pull level on, lean overflow, device-driven batches) run
-  // k_bu_full (structured-buffer rows, wave-private list queues; bitpar/pull_full.hpp) instead
-  // of k_bu_narrow
-  int full = 1;
-  // done rows are never read (k_bu_full): pulls probe a level-start snapshot of the done bitmap
-  // instead of gathering done neighbours' rows, and the rows of vertices finishing on an
-  // unfiltered pull level are not written (a push level right after gets them restored)
-  int dskip = 1;
-  // tiled first pull level: the tail push after the tiles, into the output rows (one GPU, no
-  // chunked exchange; k_push_tail_after) instead of into acc rows every tile vertex reads
-  // (RMAT-26 / 1024 groups: level 2 12.5 -> 10.95 ms, 20.7-21.3 -> 19.1-19.8 ms per step)
-  int push_after = 1;
-  // dskip on the non-lean unfiltered full pulls too (RMAT-26 level 3: 5.80 -> 5.68 ms, 1 GB of
-  // row stores fewer; see level_bu)
-  int dskip3 = 1;
-  // two-pass chunk scheduling of the wide vertices on early-exit levels (k_chunk_first):
-  // RMAT-26 / 1024 groups level 3 5.70 -> 5.30 ms
-  int chunk2 = 1;
-  // wide threshold of the first pull level for passes of <= 4 words (no tiles there) while
-  // SolverOptions::wide_degree is at its default, on graphs of >= 2^23 non-isolated vertices:
-  // RMAT-26, level 2, 128 groups 6.54 -> 6.01 ms, 256 groups 7.49 -> 7.11 ms (32 -> 128; 512 and
-  // 2048 slower; RMAT-22 prefers 32-64). 0: wide_degree as given
-  int wide_few = 128;
-  // prefix bound of the untiled first pull level (ids below it are pulled, the frontier vertices
-  // at or above it push; <= 458752, the LDS hub bitmap's bound). 0: from the batch's source
-  // count (BitparSolver::pfx_bound)
-  int pfx_h = 0;
-  // pull levels probe the any-visited bitmap before a neighbour's row while fewer than this
-  // fraction of the edges lead to visited vertices (ev < filter_frac * nnz)
-  double filter_frac = 0.5;
-  // code_deg of the tiled level: codes are cheap there (a 4-byte load and LDS ORs instead of a
-  // row gather), so rows with up to ~12 expected bits are worth a try (RMAT-26 level 2: 3 ->
-  // 12: 13.85 -> 13.32 ms)
-  double tiles_code_deg = 12.0;
-  std::string dirs;    // forced per-level directions 'T'/'B' (tests, experiments)
-
-  void set(const std::string& key, const std::string& value);
-  void parse(const std::string& spec);  // "k=v,k=v" (or ";")
-  static const Tuning& process_default();  // defaults + MSBFS_TUNE, read once per process
-};
 
 // The runtime loads a translation unit's code object on the first launch of one of its kernels:
 // 1.5-2.8 ms each for the solver's units (hipLaunchKernel in a runtime trace of the first run,
@@ -140,6 +69,8 @@ inline void load_code_objects(hipStream_t s) {
   load_code_hybrid(s);
   load_code_tiles(s);
 }
+
+struct ChunkDesc;  // (bitpar/pull.hpp)
 
 class BitparSolver final : public Solver {
  public:
@@ -209,6 +140,7 @@ class BitparSolver final : public Solver {
     // a level skipped rows: every later pull level of the batch probes dsnap_ (re-snapshotted
     // at the start of the first pull level after each skipping level)
     bool skipped_any = false, resnap = false;
+    char kind = 0;  // the last pull level's PullPlan::kind (its level record's)
   };
   struct Small {
     unsigned long long* F;
@@ -253,8 +185,72 @@ class BitparSolver final : public Solver {
   // ---- bitpar_pull.hip: one bottom-up level (returns the counter-slab rows it wrote)
   template <int W, bool COUNT>
   int level_bu(Loop& S, hipStream_t s);
+  // One pull level in flight: its plan and what the stages hand on to each other.
+  struct BuLevel {
+    PullPlan p;
+    const uint64_t* R;      // read buffer vis_[cur]
+    uint64_t* O;            // the other one, written
+    const uint64_t* alive;
+    Small sm;
+    int rows = 0;           // slab rows written by this level's counting kernels so far
+    int32_t H = kPfxH;      // prefix bound (see pfx_bound)
+    const uint32_t* snap = nullptr;    // any-visited snapshot of a lazy batch's first pull
+    const uint32_t* dsnap = nullptr;   // done snapshot (done_probe), probed where p.probe
+    const uint32_t* dprobe = nullptr;
+    const uint32_t* codes = nullptr;   // sparse row codes from code_from on
+    int32_t code_from = INT32_MAX;     // (kNoCodes)
+    const int32_t* plen = nullptr;     // prefix lengths of the per-vertex prefix pull
+  };
+  PlanGraph plan_graph() {
+    return PlanGraph{g_.n, n_eff(), g_.nnz, g_.rows_sorted, g_.old2new != nullptr, full_pull()};
+  }
+  PlanLevel plan_level(const Loop& S) const;
+  // the stages of level_bu, in order
+  void bu_build_lists(Loop& S, BuLevel& L, hipStream_t s);
+  void bu_snapshots(Loop& S, BuLevel& L, hipStream_t s);
+  template <int W>
+  void bu_codes(Loop& S, BuLevel& L, hipStream_t s);
+  template <int W>
+  void bu_tail_push(Loop& S, BuLevel& L, hipStream_t s);
   template <int W, bool COUNT>
-  bool bu_batch_ok(const Loop& S) const;
+  void bu_narrow(Loop& S, BuLevel& L, hipStream_t s);
+  template <int W>
+  void bu_chunks(Loop& S, BuLevel& L, const ChunkDesc* d, const int64_t* np, int64_t maxc,
+                 hipStream_t s);
+  template <int W, bool COUNT>
+  void bu_wide(Loop& S, BuLevel& L, hipStream_t s);
+  // the one host-side launcher of k_bu_narrow / k_bu_full (any instantiation `k`)
+  struct PullArgs {
+    const int32_t* list;
+    int64_t nact;
+    const uint64_t* R;
+    uint64_t* O;
+    const uint64_t* alive;
+    int32_t *act2, *actw2, *fl2;
+    Ctr* ctr;
+    uint32_t* slab;
+    // optional
+    int32_t filter_from = INT32_MAX;  // (k_bu_narrow)
+    uint64_t* pacc = nullptr;
+    const int32_t* stamp = nullptr;
+    int32_t epoch = 0;
+    const int32_t* plen = nullptr;
+    const uint32_t* nact_dev = nullptr;
+    const uint32_t* snap = nullptr;
+    BuGate gate{};
+    const uint32_t* dprobe = nullptr;  // (k_bu_full)
+    int flags = 0;
+  };
+  template <class K>
+  void launch_narrow(K k, int grid, int block, const PullArgs& a, hipStream_t s);
+  template <class K>
+  void launch_full(K k, int grid, const PullArgs& a, hipStream_t s);
+  template <int W, bool COUNT>
+  bool bu_batch_ok(const Loop& S) {
+    PlanLevel l = plan_level(S);
+    l.forced = !S.plan.empty() || tun_.dirs.size() > S.level;
+    return pull_batch_ok(plan_graph(), tun_, COUNT, l);
+  }
   template <int W, bool COUNT>
   void bu_batch(Loop& S, RunStats* st, hipStream_t s);
   const int32_t* prefix_lens(int32_t H, hipStream_t s);
@@ -282,10 +278,9 @@ class BitparSolver final : public Solver {
   // buffers; nullptr for fewer than 8 words, or when they do not fit in HBM)
   const TileSet* pfx_tiles(int W, int part, int nparts, hipStream_t s);
   // some word count of this solver may take the tiled first pull level (the graph-side half of
-  // level_bu's `tiled` test; pfx_tiles adds the word-count half: W >= 4 and W >= tiles_w)
-  bool tiles_possible() const {
-    return tun_.tiles && tun_.pfx == 2 && g_.rows_sorted && g_.n <= INT32_MAX && maxW_ >= 4 &&
-           maxW_ >= tun_.tiles_w;
+  // wants_tiles; pfx_tiles adds the word-count half: W >= 4 and W >= tiles_w)
+  bool tiles_possible() {
+    return tun_.tiles && prefix_capable(plan_graph(), tun_) && maxW_ >= 4 && maxW_ >= tun_.tiles_w;
   }
   template <int W>
   int tiles_pull(Loop& S, hipStream_t s, const uint64_t* R, uint64_t* O, const uint32_t* snap,
@@ -369,7 +364,6 @@ class BitparSolver final : public Solver {
   }
 
   // ---- fixed policy constants (formerly environment knobs; measured, see README)
-  static constexpr int kWideLater = 1024;     // wide split after the first bottom-up level
   static constexpr int kTdGrid = 1024;        // blocks of the device-driven batches' kernels
   static constexpr int64_t kTdWideFrontier = 393216;  // (one word: 5 blocks per CU from here)
   static constexpr int kTdRed = 6;            // fused levels per k_level_reduce_multi launch
@@ -381,10 +375,7 @@ class BitparSolver final : public Solver {
   // after a few levels (uniform n = 16M, m = 128M, 1024 groups: 29.6 ms vs 32.3 ms fused)
   static constexpr double kTdFusedDeg = 8.0;
   static constexpr int kBatch = 64;  // most levels per device-driven batch
-  static constexpr int kLeanLevel = 3;  // first pull level (1-based) that may run the lean pass
-  // k_bu_full: the all-zero row n is an int32 vertex index (row n + 1 is scratch), so graphs
-  // with n > INT32_MAX - 2 keep k_bu_narrow
-  bool full_pull() const { return tun_.full && g_.n <= (int64_t)INT32_MAX - 2; }
+  bool full_pull() const { return full_pull_ok(tun_, g_.n); }
 
   const DeviceGraph& g_;
   Tuning tun_;

@@ -33,6 +33,7 @@
 
 #include "common.hpp"
 #include "pull.hpp"
+#include "pull_plan.hpp"
 
 namespace msbfs {
 namespace bp {
@@ -50,7 +51,7 @@ constexpr int kTileWeight = 1024;   // entries + kVertexWeight * vertices per ti
 constexpr int kBigPrefix = 1024;    // more prefix entries: partial tiles
 constexpr int kPartialEntries = 1024;
 constexpr int kTileBlock = 1024;    // one block per CU: the hub bitmap + 16 waves' rows
-constexpr int kTileHubW = 14336;    // hub bitmap words (ids < 458752, the prefix bound)
+constexpr int kTileHubW = kHubW;    // hub bitmap words (ids < kPfxH = 458752, the prefix bound)
 
 // vertices per tile (the wave's accumulator rows: VT x W words, 4 KB at W = 16; the same tiles
 // serve every word count) and the weight of a vertex besides its entries

@@ -81,7 +81,6 @@ int32_t BitparSolver::code_bound(double min_deg) {
 // 16 groups at 32768-131072 (3.38 -> 3.02 ms), RMAT-22 / 64 groups near 131072, RMAT-26 / 128
 // groups (2 words) at the hub bitmap's bound.
 int32_t BitparSolver::pfx_bound_n(int W, int64_t nsrc) {
-  constexpr int32_t kPfxH = 14336 * 32;  // (the LDS hub bitmap's bound, see level_bu)
   if (tun_.pfx_h > 0) return std::min(tun_.pfx_h, kPfxH);
   if (nsrc <= 0) return kPfxH;
   // (>= 2^28 vertices: 1 / 32 whatever the words, the pull's column stream and the push's
@@ -105,8 +104,7 @@ void BitparSolver::prepare(hipStream_t s) {
   load_code_objects(s);
   (void)num_cus();
   const int64_t ne = n_eff();
-  constexpr int32_t kPfxH = 14336 * 32;  // (the prefix pull's bound, see level_bu)
-  if (g_.rows_sorted && g_.n <= INT32_MAX && tun_.pfx == 2) {
+  if (prefix_capable(plan_graph(), tun_)) {
     prefix_lens(kPfxH, s);
     if (tiles_possible()) (void)pfx_tiles(maxW_, 0, 1, s);  // (the first pull level's tiles)
   }
@@ -138,37 +136,27 @@ void BitparSolver::prepare(hipStream_t s) {
 void BitparSolver::prepare_queries(int64_t K, const int64_t* qoff, const int32_t* qids,
                                    hipStream_t s) {
   if (K <= 0) return;
+  const int mw = std::min(maxW_, opt.max_words);
   // the pinned staging of the batches' masks and source pairs (start_batch): pinning host
   // memory on the first run cost ~1.9 ms of its level 1 (RMAT-26 / 1024 groups, round 6)
   {
     int64_t np_max = 1;
-    for (int64_t k0 = 0; k0 < K;) {
-      int w = 1;
-      while (w * 64 < K - k0 && w < std::min(maxW_, opt.max_words)) w <<= 1;
-      const int64_t nb = std::min<int64_t>(K - k0, 64 * w);
-      np_max = std::max<int64_t>(np_max, qoff[k0 + nb] - qoff[k0]);
-      k0 += nb;
-    }
+    for (Batch b = batch_at(K, 0, mw); b.k0 < K; b = batch_at(K, b.k0 + b.nb, mw))
+      np_max = std::max<int64_t>(np_max, qoff[b.k0 + b.nb] - qoff[b.k0]);
     const size_t hbytes = 32 * sizeof(uint64_t) + (size_t)np_max * 2 * sizeof(int32_t);
     if (!hsrc_ || hsrc_->bytes < hbytes) hsrc_ = std::make_unique<PinnedBuf>(hbytes + hbytes / 2);
     pairs_.ensure((size_t)np_max * 2 * sizeof(int32_t));
   }
-  if (!(g_.rows_sorted && g_.n <= INT32_MAX && tun_.pfx == 2)) {
+  if (!prefix_capable(plan_graph(), tun_)) {
     MSBFS_HIP_CHECK(hipStreamSynchronize(s));
     return;
   }
-  for (int64_t k0 = 0; k0 < K;) {
-    int w = 1;
-    while (w * 64 < K - k0 && w < std::min(maxW_, opt.max_words)) w <<= 1;
-    const int64_t nb = std::min<int64_t>(K - k0, 64 * w);
-    const bool tiled = tiles_possible() && w >= 4 && w >= tun_.tiles_w;
-    if (!tiled) {
-      int64_t nsrc = 0;
-      for (int64_t j = qoff[k0]; j < qoff[k0 + nb]; ++j) nsrc += qids[j] >= 0 && qids[j] < g_.n;
-      prefix_lens(pfx_bound_n(w, nsrc), s);
-      break;
-    }
-    k0 += nb;
+  for (Batch b = batch_at(K, 0, mw); b.k0 < K; b = batch_at(K, b.k0 + b.nb, mw)) {
+    if (tiles_possible() && b.w >= 4 && b.w >= tun_.tiles_w) continue;  // (tiled)
+    int64_t nsrc = 0;
+    for (int64_t j = qoff[b.k0]; j < qoff[b.k0 + b.nb]; ++j) nsrc += qids[j] >= 0 && qids[j] < g_.n;
+    prefix_lens(pfx_bound_n(b.w, nsrc), s);
+    break;
   }
   MSBFS_HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -206,403 +194,344 @@ void BitparSolver::fix_done_rows(Loop& S, hipStream_t s) {
   MSBFS_HIP_CHECK(hipGetLastError());
 }
 
-template <int W, bool COUNT>
-int BitparSolver::level_bu(Loop& S, hipStream_t s) {
-  using L = Lay<W>;
-  const int64_t n = g_.n;
-  const Small sm = small();
-  const int grid = kMaxGrid;
-  int rows = 0;  // slab rows written by this level's counting kernels
-  uint64_t* R = vis_[S.cur].as<uint64_t>();
-  uint64_t* O = vis_[S.cur ^ 1].as<uint64_t>();
-  const uint64_t* alive = sm.alive[S.alv];
-  if (S.old_stale) {
-    // fused top-down levels wrote only vis_[cur]; pulls write the other buffer's rows of the
-    // active vertices and read both buffers' rows of the finished ones afterwards
-    const size_t vb = (size_t)std::max<int64_t>(n_eff(), 1) * W * sizeof(uint64_t);
-    MSBFS_HIP_CHECK(hipMemcpyAsync(O, R, vb, hipMemcpyDeviceToDevice, s));
-    S.old_stale = false;
-  }
-  const int next_wide = std::max(opt.wide_degree, kWideLater);
-  // the first pull level at level 2 with the prefix pull streams static vertex tiles
-  // (bitpar/tiles.hpp) instead of pulling per vertex from active lists
-  constexpr int kHubW = 14336, kHubBig = 32768;
-  const bool tiled = !COUNT && W >= 4 && W >= tun_.tiles_w && tun_.tiles && tun_.pfx == 2 && S.bu_levels == 0 &&
-                     S.level == 2 && g_.rows_sorted && n <= INT32_MAX &&
-                     n > (int64_t)kHubBig * 32 * 4 &&
-                     ((S.lazy && S.bu_levels == 0) || (double)S.ev < tun_.filter_frac * (double)g_.nnz) &&
-                     pfx_tiles(W, S.part, S.nparts, s) != nullptr;
-  S.fl_bitmap = false;  // this level writes its own frontier (list, or bitmap when tiled)
-  // The untiled prefix level with a low prefix bound (few sources, see pfx_bound) splits its
-  // lists by prefix length (k_build_active): most vertices of degree > wide_few then have short
-  // prefixes, which the per-vertex pull handles in a few steps instead of a hub chunk each.
-  // RMAT-30 / 32 groups (H ~32K): 53.3 -> 51.2 ms per step (level 2 27.0 -> 23.5, levels 3-4
-  // +1.4); RMAT-26 / 16 groups (H ~84K) 4.99 -> 4.92; with H >= ~300K (64+ groups on RMAT-26)
-  // 0.4-0.6 ms slower, so only below H = 131072. (The predicate is `pfx` below, evaluated
-  // before the level's state moves on.)
-  constexpr int32_t kHubN = kHubW * 32;
-  const bool pfx_lists = !tiled && tun_.pfx == 2 && S.bu_levels == 0 && S.level == 2 &&
-                         pfx_bound<W>(S) <= 131072 &&
-                         ((S.lazy && S.bu_levels == 0) ||
-                          (double)S.ev < tun_.filter_frac * (double)g_.nnz) &&
-                         n > (int64_t)kHubN * 4 && n > (int64_t)kHubBig * 32 * 4 &&
-                         g_.rows_sorted && n <= INT32_MAX;
-  if (!S.have_active && !tiled) {
-    // after the first bottom-up level most vertices exit early: a whole wave per chunk pays
-    // off only for much higher degrees, so later lists are split at a higher threshold
-    // (wide_few only on big graphs: RMAT-22 / 64 groups ran level 2 in 0.66 ms at 32 or 64 and
-    // 0.76-0.83 ms at 128; the narrow pull's long rows then have too few vertices to hide behind)
-    // (lists split by prefix length on a graph of >= 2^28 non-isolated vertices: half of it;
-    // RMAT-30 / 32 groups 51.1 -> 49.5 ms at 64, 49.8 at 48, 52.6 at 32 prefix entries, while
-    // RMAT-26 / 16 groups keeps 128: 4.70 ms, 4.84 at 96, 4.95 at 64)
-    const bool few = W <= 4 && tun_.wide_few > 0 && opt.wide_degree == kDefaultWideDegree &&
-                     n_eff() >= ((int64_t)1 << 23);
-    const int wide0 = S.bu_levels != 0 ? next_wide
-                      : !few ? opt.wide_degree
-                      : (pfx_lists && n_eff() >= ((int64_t)1 << 28)) ? std::max(1, tun_.wide_few / 2)
-                                                                      : tun_.wide_few;
-    k_build_active<4096><<<grid_for(S.cnt, 4096, INT32_MAX), kBlock, 0, s>>>(
-        S.cnt, S.part, S.nparts, g_.rowptr, done_.as<uint32_t>(), wide0, act_[0].as<int32_t>(),
-        actw_[0].as<int32_t>(), ctr_.as<Ctr>(),
-        pfx_lists ? prefix_lens(pfx_bound<W>(S), s) : nullptr,
-        (pfx_lists && g_.old2new) ? n_eff() : -1);  // (degree-relabelled: no isolated id < n_eff)
-    MSBFS_HIP_CHECK(hipGetLastError());
-    const HostCtr c = read_ctr(s);
-    S.nact = c.act2;
-    S.nactw = c.actw2;
-    S.have_active = true;
-    MSBFS_HIP_CHECK(hipMemsetAsync(ctr_.p, 0, sizeof(Ctr), s));
-  }
-  const bool first_bu = S.bu_levels == 0;
-  ++S.bu_levels;
-  if (S.fsrc_acc) {
-    // bottom-up does not read frontier bits; clear the pending top-down ones so acc_[ac]
-    // is all-zero and can collect the wide vertices' chunk results
-    k_zero_acc<W><<<grid_for(S.nf * L::G, kBlock), kBlock, 0, s>>>(
-        fl_[S.fc].as<int32_t>(), S.nf, acc_[S.ac].as<uint64_t>());
-    MSBFS_HIP_CHECK(hipGetLastError());
-  }
-  // lazy batch, first pull level: rows of vertices nobody visited yet may be stale, so every
-  // gathered row must be one of a visited vertex (always filter), and probes / own rows use a
-  // snapshot of the any-visited bitmap (a vertex first visited during the level may be
-  // probed before its row is written). From the next pull level on the read buffer holds
-  // this level's rows, valid for every vertex a pull can reach (see start_batch).
-  const bool lazy_first = S.lazy && first_bu;
-  const uint32_t* snap = nullptr;
-  if (lazy_first) {
+PlanLevel BitparSolver::plan_level(const Loop& S) const {
+  PlanLevel l;
+  l.level = S.level;
+  l.stop_level = S.stop_level;
+  l.bu_levels = S.bu_levels;
+  l.nparts = S.nparts;
+  l.lazy = S.lazy;
+  l.lean_off = S.lean_off;
+  l.keep_rows = S.keep_rows;
+  l.skipped_any = S.skipped_any;
+  l.on_chunk = (bool)S.on_chunk;
+  l.have_active = S.have_active;
+  l.old_stale = S.old_stale;
+  l.fsrc_acc = S.fsrc_acc;
+  l.ev = S.ev;
+  l.ef0 = S.ef0;
+  l.nact = S.nact;
+  l.nactw = S.nactw;
+  l.na = S.na;
+  return l;
+}
+
+template <class K>
+void BitparSolver::launch_narrow(K k, int grid, int block, const PullArgs& a, hipStream_t s) {
+  k<<<grid, block, 0, s>>>(a.list, a.nact, g_.rowptr, g_.col, a.R, a.O, a.alive, small().gmask,
+                           done_.as<uint32_t>(), a.act2, a.fl2, a.ctr, anyvis_.as<uint32_t>(),
+                           a.filter_from, a.actw2, std::max(opt.wide_degree, kWideLater), a.slab,
+                           a.pacc, a.stamp, a.epoch, a.plen, a.nact_dev, a.snap, a.gate);
+}
+template <class K>
+void BitparSolver::launch_full(K k, int grid, const PullArgs& a, hipStream_t s) {
+  k<<<grid, kBlock, 0, s>>>(a.list, a.nact, g_.rowptr, g_.col, a.R, a.O, g_.n, a.alive,
+                            small().gmask, done_.as<uint32_t>(), a.act2, a.fl2, a.ctr,
+                            anyvis_.as<uint32_t>(), a.actw2, std::max(opt.wide_degree, kWideLater),
+                            a.slab, a.nact_dev, a.gate, a.dprobe, a.flags);
+}
+
+// the first pull level of a batch (or the first after push levels) builds its active lists
+void BitparSolver::bu_build_lists(Loop& S, BuLevel& L, hipStream_t s) {
+  const PullPlan& p = L.p;
+  k_build_active<4096><<<grid_for(S.cnt, 4096, INT32_MAX), kBlock, 0, s>>>(
+      S.cnt, S.part, S.nparts, g_.rowptr, done_.as<uint32_t>(), p.wide0, act_[0].as<int32_t>(),
+      actw_[0].as<int32_t>(), ctr_.as<Ctr>(), p.pfx_lists ? prefix_lens(L.H, s) : nullptr,
+      (p.pfx_lists && g_.old2new) ? n_eff() : -1);  // (degree-relabelled: no isolated id < n_eff)
+  MSBFS_HIP_CHECK(hipGetLastError());
+  const HostCtr c = read_ctr(s);
+  S.nact = c.act2;
+  S.nactw = c.actw2;
+  S.have_active = true;
+  MSBFS_HIP_CHECK(hipMemsetAsync(ctr_.p, 0, sizeof(Ctr), s));
+}
+
+// the any-visited snapshot of a lazy batch's first pull and the done snapshot of dskip
+void BitparSolver::bu_snapshots(Loop& S, BuLevel& L, hipStream_t s) {
+  const PullPlan& p = L.p;
+  if (p.lazy_first) {
     MSBFS_HIP_CHECK(hipMemcpyAsync(asnap_.p, anyvis_.p, anyvis_.bytes, hipMemcpyDeviceToDevice, s));
-    snap = asnap_.as<uint32_t>();
+    L.snap = asnap_.as<uint32_t>();
   }
-  // filtered levels probe the any-visited bitmap before gathering a neighbour's row (while
-  // fewer than filter_frac of the edges lead to visited vertices, and always on a lazy batch's
-  // first pull); filter_from = first id that is probed (0) or INT32_MAX (no probes)
-  const bool filter = lazy_first || (double)S.ev < tun_.filter_frac * (double)g_.nnz;
-  const int32_t filter_from = filter ? 0 : INT32_MAX;
-  // probes of the lowest ids (the hubs after degree relabelling) read an LDS copy of their
-  // bitmap words: 56 KB (ids < 458752, two blocks per CU) or, where one 1024-thread block per CU
-  // has the LDS to itself, 128 KB (ids < 1M)
-  const bool hub_lds = filter_from == 0 && n > (int64_t)kHubW * 32 * 4;
-  const bool hub_big = n > (int64_t)kHubBig * 32 * 4;
-  // counting fused into the traversal kernels (the edge-count pass keeps k_count_frontier)
-  constexpr bool FUSE = !COUNT;
-  // prefix pull + tail push on the first bottom-up level (see k_push_tail): the pulls stop at
-  // the small hub bitmap's bound H = 458752 (RMAT-26 level 2: 16.8 ms vs 18.1 at the 1M bound)
-  constexpr int32_t kPfxH = kHubW * 32;
-  const bool pfx = tun_.pfx == 2 && first_bu && S.level == 2 && hub_lds && hub_big &&
-                   g_.rows_sorted && n <= INT32_MAX;
-  // sparse row codes for the first bottom-up level after level 1 (see k_build_codes). With
-  // the prefix pull only ids < H and the tail pushers' own codes are ever read: the codes of
-  // [code_from, H) plus those of the frontier vertices >= H (not 4 bytes for every id).
-  // dskip (see done_probe): the lean pass skips the rows of the vertices it finishes; a filtered
-  // level never follows it in a batch (ev only grows), and the unfiltered kernels all probe
-  // (k_bu_full, k_bu_first, the hub chunks; not the per-vertex pulls of tun_.full = 0)
-  const bool lean_now = tun_.lean && !S.lean_off && FUSE && filter_from == INT32_MAX &&
-                        !tiled && !pfx && S.bu_levels >= kLeanLevel &&
-                        S.nact >= tun_.lean_min;
-  const bool skip_now = lean_now && !COUNT && tun_.dskip && full_pull() && !S.keep_rows;
-  // dskip3: the full pull of an unfiltered, non-lean level (RMAT-26 level 3) skips the rows of
-  // the vertices it finishes too, but probes nothing itself while no earlier level skipped (its
-  // input rows are all current); the later levels probe as after any skipping level
-  const bool skip3 = !lean_now && tun_.dskip3 && tun_.dskip && !COUNT && full_pull() &&
-                     !S.keep_rows && filter_from == INT32_MAX && !tiled && !pfx &&
-                     S.bu_levels >= 1;
-  const bool probed_before = S.skipped_any;
-  const uint32_t* dsnap =
-      (!COUNT && full_pull()) ? done_probe(S, skip_now || skip3, s) : nullptr;
-  const uint32_t* dprobe = skip3 && !probed_before ? nullptr : dsnap;
-  S.skip_pending = skip_now || skip3;
-  S.skip_alive = alive;
-  int32_t code_from = kNoCodes;
-  const uint32_t* codes = nullptr;
-  if (first_bu && S.level == 2 && tun_.codes && W >= 8 && S.ef0 > 0 && n <= INT32_MAX) {
-    const int64_t ne = n_eff();
-    code_from = (int32_t)std::min<int64_t>(
-        code_bound((tiled ? tun_.tiles_code_deg : tun_.code_deg) * (double)g_.nnz /
-                   (double)S.ef0), ne);
-    if (code_from < ne) {
-      uint32_t* cb = touched_.as<uint32_t>();  // n entries
-      const int64_t hi = pfx ? std::min<int64_t>(std::max<int64_t>(kPfxH, code_from), ne) : ne;
-      const int64_t nl = pfx ? S.nf : 0;
-      k_build_codes<W><<<grid_for(hi - code_from + nl, kBlock, 8192), kBlock, 0, s>>>(
-          R, anyvis_.as<uint32_t>(), code_from, hi, fl_[S.fc].as<int32_t>(), nl, cb);
-      MSBFS_HIP_CHECK(hipGetLastError());
-      codes = cb;
-    } else {
-      code_from = kNoCodes;
-    }
-  }
-  // prefix bound: the tiles' fixed one, or pfx_bound for the per-vertex prefix pull (plen is
-  // cached for one bound: a batch with another source count rebuilds it, one pass over the rows)
-  // (the tiles hold their entries: no prefix lengths read at run time)
-  const int32_t H = tiled ? kPfxH : pfx_bound<W>(S);
-  const int32_t* plen = pfx && !tiled ? prefix_lens(H, s) : nullptr;
-  // the untiled prefix level (few words) writes its frontier as a bitmap (fbm_tile_, as the tiled
-  // one): the next level pulls and reads no list, a push materialises it (materialize_frontier)
-  const bool fbm_out = pfx && FUSE && !tiled && S.nact + S.nactw > 0;
-  if (fbm_out) {
+  if (p.take_snapshot) L.dsnap = done_probe(S, p.skip_now || p.skip3, s);
+  L.dprobe = p.probe ? L.dsnap : nullptr;
+  S.skip_pending = p.skip_now || p.skip3;
+  S.skip_alive = L.alive;
+}
+
+// Sparse row codes (see k_build_codes). With the prefix pull only ids < H and the tail pushers'
+// own codes are ever read: the codes of [code_from, H) plus those of the frontier vertices >= H
+// (not 4 bytes for every id).
+template <int W>
+void BitparSolver::bu_codes(Loop& S, BuLevel& L, hipStream_t s) {
+  const PullPlan& p = L.p;
+  L.code_from = kNoCodes;
+  if (!p.codes) return;
+  const int64_t ne = n_eff();
+  const int32_t from = (int32_t)std::min<int64_t>(
+      code_bound(p.code_deg * (double)g_.nnz / (double)S.ef0), ne);
+  if (from >= ne) return;
+  uint32_t* cb = touched_.as<uint32_t>();  // n entries
+  const int64_t hi = p.pfx ? std::min<int64_t>(std::max<int64_t>(kPfxH, from), ne) : ne;
+  const int64_t nl = p.pfx ? S.nf : 0;
+  k_build_codes<W><<<grid_for(hi - from + nl, kBlock, 8192), kBlock, 0, s>>>(
+      L.R, anyvis_.as<uint32_t>(), from, hi, fl_[S.fc].as<int32_t>(), nl, cb);
+  MSBFS_HIP_CHECK(hipGetLastError());
+  L.codes = cb;
+  L.code_from = from;
+}
+
+// The prefix level's set-up: prefix lengths of the per-vertex pull (plen is cached for one bound:
+// a batch with another source count rebuilds it, one pass over the rows; the tiles hold their
+// entries: no prefix lengths read at run time), the frontier bitmap, and the tail push before
+// the pulls (see k_push_tail).
+template <int W>
+void BitparSolver::bu_tail_push(Loop& S, BuLevel& L, hipStream_t s) {
+  const PullPlan& p = L.p;
+  L.plen = p.pfx && !p.tiled ? prefix_lens(L.H, s) : nullptr;
+  if (p.fbm_out) {
     const int64_t nwords = (g_.n + 31) / 32;
     fbm_tile_.ensure((size_t)(nwords + 1) * sizeof(uint32_t));
     MSBFS_HIP_CHECK(hipMemsetAsync(fbm_tile_.p, 0, (size_t)nwords * sizeof(uint32_t), s));
   }
-  // (see k_push_tail_after; needs the whole level in one tiles launch and vertex part 0 of 1)
-  S.push_after = pfx && tiled && tun_.push_after && S.nparts == 1 && !S.on_chunk;
-  // no stamps for the per-vertex prefix pull at <= 4 words: it reads every vertex's pushed row
-  // (8W coalesced bytes) instead of a stamp, and the push stores no stamp per edge
-  const bool pfx_nostamp = pfx && !tiled && W <= 4;
-  if (pfx && !S.push_after) {
-    ++epoch_;
-    const int split = S.nf < 65536 ? 8 : 1;  // (see k_push_tail)
-    k_push_tail<W><<<grid_for(S.nf * 64 * split, kBlock, 8192), kBlock, 0, s>>>(
-        fl_[S.fc].as<int32_t>(), S.nf, H, g_.rowptr, g_.col, R, codes, code_from,
-        tiled ? nullptr : done_.as<uint32_t>(), S.part, S.nparts, acc_[S.ac].as<uint64_t>(),
-        (tiled || pfx_nostamp) ? nullptr : stamp_.as<int32_t>(), epoch_, split);
-    MSBFS_HIP_CHECK(hipGetLastError());
-  }
-  if (tiled) {
-    rows = tiles_pull<W>(S, s, R, O, snap, codes, code_from, rows);
+  S.push_after = p.push_after;
+  if (!p.tail_push) return;
+  ++epoch_;
+  const int split = S.nf < 65536 ? 8 : 1;  // (see k_push_tail)
+  k_push_tail<W><<<grid_for(S.nf * 64 * split, kBlock, 8192), kBlock, 0, s>>>(
+      fl_[S.fc].as<int32_t>(), S.nf, L.H, g_.rowptr, g_.col, L.R, L.codes, L.code_from,
+      p.tiled ? nullptr : done_.as<uint32_t>(), S.part, S.nparts, acc_[S.ac].as<uint64_t>(),
+      (p.tiled || p.pfx_nostamp) ? nullptr : stamp_.as<int32_t>(), epoch_, split);
+  MSBFS_HIP_CHECK(hipGetLastError());
+}
+
+// the narrow-list pull, by the plan's kind
+template <int W, bool COUNT>
+void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
+  using Lw = Lay<W>;
+  constexpr bool FUSE = !COUNT;
+  const PullPlan& p = L.p;
+  if (p.kind == PullKind::Tiled) {
+    L.rows = tiles_pull<W>(S, s, L.R, L.O, L.snap, L.codes, L.code_from, L.rows);
     if (S.push_after) {
       const int gp = grid_for(S.nf * 64, kBlock, kMaxGrid);
-      if (rows + gp > 3 * kMaxGrid) fail("tail push: counter slab rows exhausted");
+      if (L.rows + gp > 3 * kMaxGrid) fail("tail push: counter slab rows exhausted");
       k_push_tail_after<W><<<gp, kBlock, 0, s>>>(
-          fl_[S.fc].as<int32_t>(), S.nf, kPfxH, g_.rowptr, g_.col, R, codes, code_from, O,
-          fbm_tile_.as<uint32_t>(), anyvis_.as<uint32_t>(), ctr_.as<Ctr>(), slabF<W>(rows));
+          fl_[S.fc].as<int32_t>(), S.nf, kPfxH, g_.rowptr, g_.col, L.R, L.codes, L.code_from, L.O,
+          fbm_tile_.as<uint32_t>(), anyvis_.as<uint32_t>(), ctr_.as<Ctr>(), slabF<W>(L.rows));
       MSBFS_HIP_CHECK(hipGetLastError());
-      rows += gp;
+      L.rows += gp;
       S.push_after = false;
     }
     S.have_active = S.level < S.stop_level;
-  } else if (S.nact) {
-    if (pfx) {
-      // one word: 80 VGPRs, 6 waves per SIMD, so two 768-thread blocks per CU (the 56-KB hub
-      // bitmap each) instead of one 1024-thread block: RMAT-30 / 32 groups level 2 35.9 -> 32.8
-      // ms, RMAT-26 / 16 groups 3.53 -> 3.36 ms (a next-step column id prefetch measured slower:
-      // 88 VGPRs)
-      constexpr int BT = W == 1 ? 768 : 1024;
-      const int gn = grid_for(S.nact, (BT / 64) * L::VPW, 512);
+    return;
+  }
+  if (!S.nact) return;
+  PullArgs a{act_[0].as<int32_t>(), S.nact, L.R, L.O, L.alive, act_[1].as<int32_t>(),
+             actw_[1].as<int32_t>(), fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
+             slabF<W>(L.rows)};
+  a.filter_from = p.filter_from;
+  a.snap = L.snap;
+  const int gn = grid_for(S.nact, Lw::TILE, kMaxGrid);  // (the 256-thread kernels)
+  switch (p.kind) {
+    case PullKind::Prefix: {
+      constexpr int BT = pfx_block(W);
+      const int g = grid_for(S.nact, (BT / 64) * Lw::VPW, 512);
       // 4-neighbour steps: 122 VGPRs, no spills (8-neighbour steps spilled at the 128-VGPR
       // bound): RMAT-26 5.17 -> 4.96 ms (the full pulls of level 3 keep 8: 5.8 vs 6.8 ms)
-      // (FBM: frontier bitmap in place of the list, see fbm_out)
-      auto kn = FUSE ? k_bu_narrow<W, COUNT, BT, kHubW, FUSE, true, true, 4, 0, (W == 1 && BT < 1024 ? 6 : 4), true>
+      // (FBM: frontier bitmap in place of the list, see PullPlan::fbm_out)
+      auto kn = FUSE ? k_bu_narrow<W, COUNT, BT, kHubW, FUSE, true, true, 4, 0, pfx_minw(W), true>
                      : k_bu_narrow<W, COUNT, BT, kHubW, false, true, true>;
-      kn<<<gn, BT, 0, s>>>(act_[0].as<int32_t>(), S.nact, g_.rowptr, g_.col, R, O, alive,
-                           sm.gmask, done_.as<uint32_t>(), act_[1].as<int32_t>(),
-                           FUSE ? reinterpret_cast<int32_t*>(fbm_tile_.p)
-                                : fl_[S.fc ^ 1].as<int32_t>(),
-                           ctr_.as<Ctr>(),
-                           anyvis_.as<uint32_t>(), filter_from, actw_[1].as<int32_t>(),
-                           next_wide, slabF<W>(rows), acc_[S.ac].as<uint64_t>(),
-                           pfx_nostamp ? nullptr : stamp_.as<int32_t>(), epoch_, plen, nullptr,
-                           snap, BuGate{});
-      if (FUSE) rows += gn;
-    } else if (hub_lds) {
+      if (FUSE) a.fl2 = reinterpret_cast<int32_t*>(fbm_tile_.p);
+      a.pacc = acc_[S.ac].as<uint64_t>();
+      a.stamp = p.pfx_nostamp ? nullptr : stamp_.as<int32_t>();
+      a.epoch = epoch_;
+      a.plen = L.plen;
+      launch_narrow(kn, g, BT, a, s);
+      if (FUSE) L.rows += g;
+      break;
+    }
+    case PullKind::Hub: {
       constexpr int BT = 1024;
-      const int gn = grid_for(S.nact, (BT / 64) * L::VPW, 512);
-      // the narrow kernel runs one 1024-thread block per CU anyway (VGPR-bound), so its LDS
-      // has room for a 4x larger hub bitmap
-      auto kn = hub_big ? k_bu_narrow<W, COUNT, BT, kHubBig, FUSE>
-                        : k_bu_narrow<W, COUNT, BT, kHubW, FUSE>;
-      kn<<<gn, BT, 0, s>>>(act_[0].as<int32_t>(), S.nact, g_.rowptr, g_.col, R, O, alive,
-                           sm.gmask, done_.as<uint32_t>(), act_[1].as<int32_t>(),
-                           fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
-                           anyvis_.as<uint32_t>(), filter_from, actw_[1].as<int32_t>(),
-                           next_wide, slabF<W>(rows), nullptr, nullptr, 0, nullptr, nullptr, snap, BuGate{});
-      if (FUSE) rows += gn;
-    } else {
-      const int gn = grid_for(S.nact, L::TILE, grid);
-      // FILT = false: no probe code at all (fewer VGPRs) on the levels that load every row
-      const bool filt = filter_from != INT32_MAX;
-      // short first step (one row) from the third bottom-up level on, or with few words: by
-      // then most vertices are covered by their first neighbour (RMAT-26, 1024 groups: level
-      // 4 3.1 -> 2.5 ms; level 3 prefers full steps: 6.5 vs 6.7 ms)
-      const bool short1 = S.bu_levels >= 3 || W <= 4;
-      if (tun_.lean && !S.lean_off && FUSE && !filt && S.bu_levels >= kLeanLevel &&
-          S.nact >= tun_.lean_min) {
-        S.lean_ran = true;
-        // lean first pass, then the regular pull over the vertices it could not finish
-        const int gl = grid_for(S.nact, L::TILE, grid);
-        k_bu_first<W><<<gl, kBlock, 0, s>>>(
-            act_[0].as<int32_t>(), S.nact, g_.rowptr, g_.col, R, O, alive, sm.gmask,
-            done_.as<uint32_t>(), touched_.as<int32_t>(), fl_[S.fc ^ 1].as<int32_t>(),
-            ctr_.as<Ctr>(), anyvis_.as<uint32_t>(), slabF<W>(rows), first_nbr(s), dsnap,
-            skip_now ? kFlagSkipRows : 0);
-        MSBFS_HIP_CHECK(hipGetLastError());
-        rows += gl;
-        const int go = full_pull() ? full_grid<W>(gn, S.nact, true) : gn;
-        if (full_pull())
-          k_bu_full<W, full_cs<W>(), 1><<<go, kBlock, 0, s>>>(
-              touched_.as<int32_t>(), S.nact, g_.rowptr, g_.col, R, O, n, alive, sm.gmask,
-              done_.as<uint32_t>(), act_[1].as<int32_t>(), fl_[S.fc ^ 1].as<int32_t>(),
-              ctr_.as<Ctr>(), anyvis_.as<uint32_t>(), actw_[1].as<int32_t>(), next_wide,
-              slabF<W>(rows), &ctr_.as<Ctr>()->touched.v, BuGate{}, dsnap,
-              skip_now ? kFlagSkipRows : 0);
-        else
-          k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false, false, 8, 1><<<go, kBlock, 0, s>>>(
-              touched_.as<int32_t>(), S.nact, g_.rowptr, g_.col, R, O, alive, sm.gmask,
-              done_.as<uint32_t>(), act_[1].as<int32_t>(), fl_[S.fc ^ 1].as<int32_t>(),
-              ctr_.as<Ctr>(), anyvis_.as<uint32_t>(), filter_from, actw_[1].as<int32_t>(),
-              next_wide, slabF<W>(rows), nullptr, nullptr, 0, nullptr,
-              &ctr_.as<Ctr>()->touched.v, nullptr, BuGate{});
-        MSBFS_HIP_CHECK(hipGetLastError());
-        rows += go;
-      } else if (FUSE && !filt && full_pull()) {
-        auto kf = short1 ? k_bu_full<W, full_cs<W>(), 1> : k_bu_full<W, full_cs<W>(), 0>;
-        const int gf = full_grid<W>(gn, S.nact);
-        kf<<<gf, kBlock, 0, s>>>(act_[0].as<int32_t>(), S.nact, g_.rowptr, g_.col, R, O, n, alive,
-                                 sm.gmask, done_.as<uint32_t>(), act_[1].as<int32_t>(),
-                                 fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
-                                 anyvis_.as<uint32_t>(), actw_[1].as<int32_t>(), next_wide,
-                                 slabF<W>(rows), nullptr, BuGate{}, dprobe,
-                                 (skip3 ? kFlagSkipRows : 0));
-        rows += gf;
-      } else {
-        auto kn = FUSE ? (filt ? k_bu_narrow<W, COUNT, kBlock, 0, FUSE, true>
-                               : short1 ? k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false, false, 8, 1>
-                                        : k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false>)
-                       : (filt ? k_bu_narrow<W, COUNT, kBlock, 0, false, true>
-                               : k_bu_narrow<W, COUNT, kBlock, 0, false, false>);
-        kn<<<gn, kBlock, 0, s>>>(act_[0].as<int32_t>(), S.nact, g_.rowptr, g_.col, R, O, alive,
-                                 sm.gmask, done_.as<uint32_t>(), act_[1].as<int32_t>(),
-                                 fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
-                                 anyvis_.as<uint32_t>(), filter_from, actw_[1].as<int32_t>(),
-                                 next_wide, slabF<W>(rows), nullptr, nullptr, 0, nullptr, nullptr,
-                                 snap, BuGate{});
-        if (FUSE) rows += gn;
-      }
+      const int g = grid_for(S.nact, (BT / 64) * Lw::VPW, 512);
+      launch_narrow(p.hub_big ? k_bu_narrow<W, COUNT, BT, kHubBig, FUSE>
+                              : k_bu_narrow<W, COUNT, BT, kHubW, FUSE>, g, BT, a, s);
+      if (FUSE) L.rows += g;
+      break;
     }
-    MSBFS_HIP_CHECK(hipGetLastError());
+    case PullKind::Lean: {
+      // lean first pass, then the regular pull over the vertices it could not finish
+      S.lean_ran = true;
+      k_bu_first<W><<<gn, kBlock, 0, s>>>(
+          a.list, S.nact, g_.rowptr, g_.col, L.R, L.O, L.alive, L.sm.gmask, done_.as<uint32_t>(),
+          touched_.as<int32_t>(), a.fl2, a.ctr, anyvis_.as<uint32_t>(), slabF<W>(L.rows),
+          first_nbr(s), L.dsnap, p.skip_now ? kFlagSkipRows : 0);
+      MSBFS_HIP_CHECK(hipGetLastError());
+      L.rows += gn;
+      const int go = p.full ? full_grid<W>(gn, S.nact, true) : gn;
+      a.list = touched_.as<int32_t>();
+      a.slab = slabF<W>(L.rows);
+      a.nact_dev = &ctr_.as<Ctr>()->touched.v;
+      a.dprobe = L.dsnap;
+      a.flags = p.skip_now ? kFlagSkipRows : 0;
+      if (p.full) launch_full(k_bu_full<W, full_cs<W>(), 1>, go, a, s);
+      else launch_narrow(k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false, false, 8, 1>, go, kBlock, a, s);
+      L.rows += go;
+      break;
+    }
+    case PullKind::Full: {
+      const int gf = full_grid<W>(gn, S.nact);
+      a.dprobe = L.dprobe;
+      a.flags = p.skip3 ? kFlagSkipRows : 0;
+      launch_full(p.short1 ? k_bu_full<W, full_cs<W>(), 1> : k_bu_full<W, full_cs<W>(), 0>, gf, a, s);
+      L.rows += gf;
+      break;
+    }
+    default: {
+      auto kn = FUSE ? (p.filter ? k_bu_narrow<W, COUNT, kBlock, 0, FUSE, true>
+                         : p.short1 ? k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false, false, 8, 1>
+                                    : k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false>)
+                     : (p.filter ? k_bu_narrow<W, COUNT, kBlock, 0, false, true>
+                                 : k_bu_narrow<W, COUNT, kBlock, 0, false, false>);
+      launch_narrow(kn, gn, kBlock, a, s);
+      if (FUSE) L.rows += gn;
+    }
   }
-  // early exit across a vertex's chunks (coop) everywhere except on an explosive first
-  // bottom-up level (level 2: hardly any row gets covered, and round-robin chunk dealing
-  // balances the hubs better). When top-down ran longer (RMAT-30: first pull at level 3, most of
-  // every hub's groups already visited) the early exit skips most chunks.
-  const int coop = !first_bu || S.level != 2 ? 1 : 0;
-  auto launch_chunks = [&](const ChunkDesc* d, const int64_t* np, int64_t maxc) {
-    if (hub_lds) {
-      // exact chunk count = *np, read on the device (no host round trip); one block per CU
-      // with the 128-KB hub bitmap (ids < 1M) except on the prefix level, whose prefixes end
-      // at the small one's bound (two blocks per CU)
-      const bool big = hub_big && !pfx;
-      // (the prefix level without codes: LDS probes only, the next tile's ids in flight)
-      auto ck = big ? k_bu_chunks<W, 256, 1024, kHubBig>
-                    : (pfx && !codes && filter_from == 0 && !dprobe && !coop)
-                          ? k_bu_chunks<W, 256, 1024, kHubW, true>
-                          : k_bu_chunks<W, 256, 1024, kHubW>;
-      ck<<<grid_for(maxc, 16, big ? 256 : 512), 1024, 0, s>>>(
-          d, np, g_.col, R, alive, sm.gmask, acc_[S.ac].as<uint64_t>(), anyvis_.as<uint32_t>(),
-          filter_from, coop, codes, code_from, snap, dprobe);
-    } else {
-      k_bu_chunks<W, 256, kBlock, 0><<<grid_for(maxc, kWaves, 8192), kBlock, 0, s>>>(
-          d, np, g_.col, R, alive, sm.gmask, acc_[S.ac].as<uint64_t>(), anyvis_.as<uint32_t>(),
-          filter_from, coop, codes, code_from, snap, dprobe);
-    }
-    MSBFS_HIP_CHECK(hipGetLastError());
-  };
-  if (S.nactw && !tiled && coop && !pfx && tun_.chunk2) {
-    // two passes (see k_chunk_first): first chunks, then the rest of the open vertices
-    const int64_t chunks_max = S.nactw + S.ea / kChunk + 1;
-    desc_.ensure((size_t)chunks_max * sizeof(ChunkDesc));
+  MSBFS_HIP_CHECK(hipGetLastError());
+}
+
+// one launch over chunk descriptors d[0 .. *np) (exact count read on the device: no host round
+// trip), at most maxc of them
+template <int W>
+void BitparSolver::bu_chunks(Loop& S, BuLevel& L, const ChunkDesc* d, const int64_t* np,
+                             int64_t maxc, hipStream_t s) {
+  const PullPlan& p = L.p;
+  auto ck = !p.hub_lds                   ? k_bu_chunks<W, 256, kBlock, 0>
+            : p.chunk_hub_big            ? k_bu_chunks<W, 256, 1024, kHubBig>
+            : (p.chunk_pfxl && !L.codes) ? k_bu_chunks<W, 256, 1024, kHubW, true>
+                                         : k_bu_chunks<W, 256, 1024, kHubW>;
+  const int grid = !p.hub_lds ? grid_for(maxc, kWaves, 8192)
+                              : grid_for(maxc, 16, p.chunk_hub_big ? 256 : 512);
+  ck<<<grid, p.hub_lds ? 1024 : kBlock, 0, s>>>(
+      d, np, g_.col, L.R, L.alive, L.sm.gmask, acc_[S.ac].as<uint64_t>(), anyvis_.as<uint32_t>(),
+      p.filter_from, p.coop, L.codes, L.code_from, L.snap, L.dprobe);
+  MSBFS_HIP_CHECK(hipGetLastError());
+}
+
+// the wide vertices: chunk descriptors (by the plan's scheduling), chunk launches, finalize
+template <int W, bool COUNT>
+void BitparSolver::bu_wide(Loop& S, BuLevel& L, hipStream_t s) {
+  using Lw = Lay<W>;
+  constexpr bool FUSE = !COUNT;
+  const PullPlan& p = L.p;
+  if (!S.nactw || p.tiled) return;
+  const int32_t* lw = actw_[0].as<int32_t>();
+  const int64_t chunks_max = S.nactw + S.ea / kChunk + 1;
+  desc_.ensure((size_t)chunks_max * sizeof(ChunkDesc));
+  ChunkDesc* d = desc_.as<ChunkDesc>();
+  // (scan scratch behind the per-vertex counts)
+  int64_t* cnt = scan_tmp_.as<int64_t>();
+  char* t2 = (char*)scan_tmp_.p + (((size_t)S.nactw * sizeof(int64_t) + 255) & ~size_t(255));
+  const size_t tb = scan_bytes_ - (size_t)(t2 - (char*)scan_tmp_.p);
+  if (p.chunks == ChunkSched::TwoPass) {
     chunk_cnt_.ensure(sizeof(int64_t));
-    ChunkDesc* d = desc_.as<ChunkDesc>();
-    k_chunk_first<<<grid_for(S.nactw, kBlock), kBlock, 0, s>>>(
-        actw_[0].as<int32_t>(), S.nactw, g_.rowptr, d, chunk_cnt_.as<int64_t>());
+    k_chunk_first<<<grid_for(S.nactw, kBlock), kBlock, 0, s>>>(lw, S.nactw, g_.rowptr, d,
+                                                                chunk_cnt_.as<int64_t>());
     MSBFS_HIP_CHECK(hipGetLastError());
-    launch_chunks(d, chunk_cnt_.as<int64_t>(), S.nactw);
-    int64_t* cnt = scan_tmp_.as<int64_t>();
-    char* t2 = (char*)scan_tmp_.p + (((size_t)S.nactw * sizeof(int64_t) + 255) & ~size_t(255));
-    const size_t tb = scan_bytes_ - (size_t)(t2 - (char*)scan_tmp_.p);
-    k_chunk_rest_count<W><<<grid_for(S.nactw, L::TILE, grid), kBlock, 0, s>>>(
-        actw_[0].as<int32_t>(), S.nactw, g_.rowptr, R, acc_[S.ac].as<uint64_t>(), alive,
-        sm.gmask, snap, cnt);
+    bu_chunks<W>(S, L, d, chunk_cnt_.as<int64_t>(), S.nactw, s);
+    k_chunk_rest_count<W><<<grid_for(S.nactw, Lw::TILE, kMaxGrid), kBlock, 0, s>>>(
+        lw, S.nactw, g_.rowptr, L.R, acc_[S.ac].as<uint64_t>(), L.alive, L.sm.gmask, L.snap, cnt);
     MSBFS_HIP_CHECK(hipGetLastError());
     inclusive_scan_i64(cnt, offs_.as<int64_t>(), S.nactw, t2, tb, s);
     k_chunk_rest_desc<<<grid_for(S.nactw, kBlock), kBlock, 0, s>>>(
-        actw_[0].as<int32_t>(), S.nactw, offs_.as<int64_t>(), g_.rowptr, d + S.nactw);
+        lw, S.nactw, offs_.as<int64_t>(), g_.rowptr, d + S.nactw);
     MSBFS_HIP_CHECK(hipGetLastError());
-    launch_chunks(d + S.nactw, offs_.as<int64_t>() + S.nactw - 1, chunks_max - S.nactw);
-  } else if (S.nactw && !tiled) {
-    if (pfx) {  // chunks of the row prefixes with ids < H only
-      int64_t* cnt = scan_tmp_.as<int64_t>();
-      char* t2 = (char*)scan_tmp_.p + (((size_t)S.nactw * sizeof(int64_t) + 255) & ~size_t(255));
-      const size_t tb = scan_bytes_ - (size_t)(t2 - (char*)scan_tmp_.p);
-      k_prefix_chunks<<<grid_for(S.nactw, kBlock), kBlock, 0, s>>>(
-          actw_[0].as<int32_t>(), S.nactw, plen, cnt);
+    bu_chunks<W>(S, L, d + S.nactw, offs_.as<int64_t>() + S.nactw - 1, chunks_max - S.nactw, s);
+  } else {
+    if (p.chunks == ChunkSched::Prefix) {
+      k_prefix_chunks<<<grid_for(S.nactw, kBlock), kBlock, 0, s>>>(lw, S.nactw, L.plen, cnt);
       MSBFS_HIP_CHECK(hipGetLastError());
       inclusive_scan_i64(cnt, offs_.as<int64_t>(), S.nactw, t2, tb, s);
     } else {
-      frontier_degree_scan(g_.rowptr, actw_[0].as<int32_t>(), S.nactw, offs_.as<int64_t>(),
-                           scan_tmp_.p, scan_bytes_, s, kChunk);
+      frontier_degree_scan(g_.rowptr, lw, S.nactw, offs_.as<int64_t>(), scan_tmp_.p, scan_bytes_,
+                           s, kChunk);
     }
-    const int64_t chunks_max = S.nactw + S.ea / kChunk + 1;
-    desc_.ensure((size_t)chunks_max * sizeof(ChunkDesc));
-    k_chunk_desc<<<grid_for(S.nactw, kBlock), kBlock, 0, s>>>(
-        actw_[0].as<int32_t>(), S.nactw, offs_.as<int64_t>(), g_.rowptr, plen,
-        desc_.as<ChunkDesc>());
+    k_chunk_desc<<<grid_for(S.nactw, kBlock), kBlock, 0, s>>>(lw, S.nactw, offs_.as<int64_t>(),
+                                                               g_.rowptr, L.plen, d);
     MSBFS_HIP_CHECK(hipGetLastError());
-    launch_chunks(desc_.as<ChunkDesc>(), offs_.as<int64_t>() + S.nactw - 1, chunks_max);
+    bu_chunks<W>(S, L, d, offs_.as<int64_t>() + S.nactw - 1, chunks_max, s);
   }
-  if (S.nactw && !tiled) {
-    const int gw = grid_for(S.nactw, L::TILE, grid);
-    auto kw = fbm_out ? k_bu_wide_finalize<W, COUNT, FUSE, true>
-                      : k_bu_wide_finalize<W, COUNT, FUSE>;
-    kw<<<gw, kBlock, 0, s>>>(
-        actw_[0].as<int32_t>(), S.nactw, g_.rowptr, R, O, acc_[S.ac].as<uint64_t>(), alive,
-        sm.gmask, done_.as<uint32_t>(), actw_[1].as<int32_t>(), fl_[S.fc ^ 1].as<int32_t>(),
-        ctr_.as<Ctr>(), anyvis_.as<uint32_t>(), act_[1].as<int32_t>(), next_wide,
-        slabF<W>(rows), snap, fbm_out ? fbm_tile_.as<uint32_t>() : nullptr);
+  const int gw = grid_for(S.nactw, Lw::TILE, kMaxGrid);
+  auto kw = p.fbm_out ? k_bu_wide_finalize<W, COUNT, FUSE, true> : k_bu_wide_finalize<W, COUNT, FUSE>;
+  kw<<<gw, kBlock, 0, s>>>(
+      lw, S.nactw, g_.rowptr, L.R, L.O, acc_[S.ac].as<uint64_t>(), L.alive, L.sm.gmask,
+      done_.as<uint32_t>(), actw_[1].as<int32_t>(), fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
+      anyvis_.as<uint32_t>(), act_[1].as<int32_t>(), p.next_wide, slabF<W>(L.rows), L.snap,
+      p.fbm_out ? fbm_tile_.as<uint32_t>() : nullptr);
+  MSBFS_HIP_CHECK(hipGetLastError());
+  if (FUSE) L.rows += gw;
+}
+
+// One bottom-up level: the plan (bitpar/pull_plan.hpp), then its stages in order.
+template <int W, bool COUNT>
+int BitparSolver::level_bu(Loop& S, hipStream_t s) {
+  BuLevel L;
+  L.sm = small();
+  L.R = vis_[S.cur].as<uint64_t>();
+  L.O = vis_[S.cur ^ 1].as<uint64_t>();
+  L.alive = L.sm.alive[S.alv];
+  if (S.old_stale) {
+    // fused top-down levels wrote only vis_[cur]; pulls write the other buffer's rows of the
+    // active vertices and read both buffers' rows of the finished ones afterwards
+    const size_t vb = (size_t)std::max<int64_t>(n_eff(), 1) * W * sizeof(uint64_t);
+    MSBFS_HIP_CHECK(hipMemcpyAsync(L.O, L.R, vb, hipMemcpyDeviceToDevice, s));
+    S.old_stale = false;
+  }
+  const PlanGraph g = plan_graph();
+  const PlanOpts o{opt.wide_degree, kDefaultWideDegree};
+  PlanLevel l = plan_level(S);
+  // (asking for the tiles builds them on first use: only once the level wants them)
+  const bool tiled =
+      wants_tiles(g, tun_, W, COUNT, l) && pfx_tiles(W, S.part, S.nparts, s) != nullptr;
+  l.H = L.H = tiled ? kPfxH : pfx_bound<W>(S);
+  S.fl_bitmap = false;  // this level writes its own frontier (list, or bitmap when tiled)
+  plan_lists(L.p, g, o, tun_, W, l, tiled);
+  if (L.p.build_lists) bu_build_lists(S, L, s);
+  l.nact = S.nact;
+  l.nactw = S.nactw;
+  L.p = plan_pull(g, o, tun_, W, COUNT, l, tiled);
+  const PullPlan& p = L.p;
+  ++S.bu_levels;
+  S.kind = (char)p.kind;
+  if (S.fsrc_acc) {
+    // bottom-up does not read frontier bits; clear the pending top-down ones so acc_[ac]
+    // is all-zero and can collect the wide vertices' chunk results
+    k_zero_acc<W><<<grid_for(S.nf * Lay<W>::G, kBlock), kBlock, 0, s>>>(
+        fl_[S.fc].as<int32_t>(), S.nf, acc_[S.ac].as<uint64_t>());
     MSBFS_HIP_CHECK(hipGetLastError());
-    if (FUSE) rows += gw;
   }
-  if constexpr (!FUSE) {
+  bu_snapshots(S, L, s);
+  bu_codes<W>(S, L, s);
+  bu_tail_push<W>(S, L, s);
+  bu_narrow<W, COUNT>(S, L, s);
+  bu_wide<W, COUNT>(S, L, s);
+  if constexpr (COUNT) {
+    // the edge-counting mode's count pass (the traversal kernels fuse the plain counts):
     // new frontier bits = Wb & ~R (both still in place: the swap is below)
-    const int gc = grid_for(S.nact + S.nactw, L::TILE, grid);
+    const int gc = grid_for(S.nact + S.nactw, Lay<W>::TILE, kMaxGrid);
     k_count_frontier<W, COUNT, true><<<gc, kBlock, 0, s>>>(
-        fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(), g_.rowptr, O, R, slabF<W>(rows),
-        slabE<W>(rows));
+        fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(), g_.rowptr, L.O, L.R, slabF<W>(L.rows),
+        slabE<W>(L.rows));
     MSBFS_HIP_CHECK(hipGetLastError());
-    rows += gc;
+    L.rows += gc;
   }
   std::swap(act_[0], act_[1]);
   std::swap(actw_[0], actw_[1]);
   S.cur ^= 1;
   S.fsrc_acc = false;
-  S.osnap_next = lazy_first;
-  if (fbm_out) S.fl_bitmap = true;
-  return rows;
-}
-
-// Pull levels that bu_batch may run: the third pull level on (lists split at kWideLater, every
-// row pulled without probes, no lean pass), active lists of at most tun_.bu_max vertices, no
-// forced directions and no edge counting (k_count_frontier needs per-level host sizes).
-template <int W, bool COUNT>
-bool BitparSolver::bu_batch_ok(const Loop& S) const {
-  // (fsrc_acc: a push level came last; level_bu first clears the accumulator entries of its
-  // frontier, which later pulls and the next batch expect all-zero)
-  if (COUNT || tun_.bu_max <= 0 || tun_.batch <= 1 || !S.have_active || S.bu_levels < 2 ||
-      S.old_stale || S.fsrc_acc || S.na > tun_.bu_max || !S.plan.empty() || tun_.dirs.size() > S.level)
-    return false;
-  if ((double)S.ev < tun_.filter_frac * (double)g_.nnz) return false;  // level_bu would filter
-  if (tun_.lean && !S.lean_off && S.nact >= tun_.lean_min) return false;
-  return S.stop_level == 0xFFFFFFFFu || S.level + 2 <= S.stop_level;
+  S.osnap_next = p.lazy_first;
+  if (p.fbm_out) S.fl_bitmap = true;
+  return L.rows;
 }
 
 // A batch of up to bu_next_ pull levels with no host synchronisation (the late levels of
@@ -632,7 +561,6 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
                              : grid_for(S.nact + S.nactw, L::TILE, kMaxGrid);
   const int gw = S.nactw ? grid_for(S.nactw, L::TILE, kMaxGrid) : 0;
   const int rows = gn + gw, rg = std::max(1, std::min(64, rows / 32));
-  const int next_wide = std::max(opt.wide_degree, kWideLater);
   const double alpha = alpha_eff();
   const uint32_t level0 = S.level;
   const auto t0 = std::chrono::steady_clock::now();
@@ -645,16 +573,13 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
   auto launch = [&](int grid, const int32_t* list, const uint64_t* R, uint64_t* O,
                     const uint64_t* alive, int32_t* fl_out, Ctr* out, uint32_t* slab,
                     const uint32_t* len, const BuGate& gate, int p) {
-    if (full)
-      k_bu_full<W, full_cs<W>(), 1><<<grid, kBlock, 0, s>>>(
-          list, 0, g_.rowptr, g_.col, R, O, g_.n, alive, sm.gmask, done_.as<uint32_t>(),
-          act_[p ^ 1].as<int32_t>(), fl_out, out, anyvis_.as<uint32_t>(),
-          actw_[p ^ 1].as<int32_t>(), next_wide, slab, len, gate, dsnap, 0);
-    else
-      kn<<<grid, kBlock, 0, s>>>(list, 0, g_.rowptr, g_.col, R, O, alive, sm.gmask,
-                                 done_.as<uint32_t>(), act_[p ^ 1].as<int32_t>(), fl_out, out,
-                                 anyvis_.as<uint32_t>(), INT32_MAX, actw_[p ^ 1].as<int32_t>(),
-                                 next_wide, slab, nullptr, nullptr, 0, nullptr, len, nullptr, gate);
+    PullArgs a{list, 0, R, O, alive, act_[p ^ 1].as<int32_t>(), actw_[p ^ 1].as<int32_t>(),
+               fl_out, out, slab};
+    a.nact_dev = len;
+    a.gate = gate;
+    a.dprobe = dsnap;
+    if (full) launch_full(k_bu_full<W, full_cs<W>(), 1>, grid, a, s);
+    else launch_narrow(kn, grid, kBlock, a, s);
   };
   for (int i = 0; i < K; ++i) {
     const BuGate gate{slots + i, opt.beta, alpha, i == 0 ? 1 : 0};
@@ -692,6 +617,7 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
       rec.batch = (int32_t)st->batches;
       rec.level = (int32_t)(level0 + 1 + i);
       rec.dir = 'B';
+      rec.kind = (char)batch_kind(plan_graph());
       rec.nf = h[i].fl2.v;
       rec.ef = (int64_t)h[i].ef2.v;
       rec.nf_next = h[i + 1].fl2.v;
@@ -729,8 +655,6 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
   template void BitparSolver::fix_done_rows<WW>(Loop&, hipStream_t);     \
   template int BitparSolver::level_bu<WW, false>(Loop&, hipStream_t);    \
   template int BitparSolver::level_bu<WW, true>(Loop&, hipStream_t);     \
-  template bool BitparSolver::bu_batch_ok<WW, false>(const Loop&) const; \
-  template bool BitparSolver::bu_batch_ok<WW, true>(const Loop&) const;  \
   template void BitparSolver::bu_batch<WW, false>(Loop&, RunStats*, hipStream_t);
 MSBFS_BP_FOR_W(MSBFS_BP_INST)
 #undef MSBFS_BP_INST

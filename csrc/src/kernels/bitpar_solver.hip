@@ -4,7 +4,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "bitpar/init.hpp"
@@ -12,89 +11,6 @@
 
 namespace msbfs {
 namespace bp {
-
-// ---- tuning ----------------------------------------------------------------------------------
-namespace {
-double to_num(const std::string& key, const std::string& v) {
-  char* end = nullptr;
-  const double x = strtod(v.c_str(), &end);
-  if (v.empty() || !end || *end) fail("tuning: bad value '" + v + "' for " + key);
-  return x;
-}
-}  // namespace
-
-void Tuning::set(const std::string& key, const std::string& v) {
-  if (key == "gamma") gamma = to_num(key, v);
-  else if (key == "gamma2") {
-    gamma2 = to_num(key, v);
-    gamma2_auto = false;
-  }
-  else if (key == "pfx") {
-    pfx = (int)to_num(key, v);
-    if (pfx != 0 && pfx != 2) fail("tuning: pfx must be 0 (whole rows) or 2 (prefix pull)");
-  } else if (key == "codes") codes = (int)to_num(key, v);
-  else if (key == "code_deg") code_deg = to_num(key, v);
-  else if (key == "lean") lean = (int)to_num(key, v);
-  else if (key == "lean_min") lean_min = (int64_t)to_num(key, v);
-  else if (key == "lazy") lazy = (int)to_num(key, v);
-  else if (key == "td_fused") td_fused = (int)to_num(key, v);
-  else if (key == "td_bm") td_bm = (int64_t)to_num(key, v);
-  else if (key == "batch") {
-    batch = (int)to_num(key, v);
-    if (batch < 1 || batch > 64) fail("tuning: batch must be in [1, 64]");
-  } else if (key == "bu_max") bu_max = (int64_t)to_num(key, v);
-  else if (key == "tiles") tiles = (int)to_num(key, v);
-  else if (key == "tiles_code_deg") tiles_code_deg = to_num(key, v);
-  else if (key == "full") full = (int)to_num(key, v);
-  else if (key == "dskip") dskip = (int)to_num(key, v);
-  else if (key == "push_after") push_after = (int)to_num(key, v);
-  else if (key == "dskip3") dskip3 = (int)to_num(key, v);
-  else if (key == "chunk2") chunk2 = (int)to_num(key, v);
-  else if (key == "wide_few") wide_few = (int)to_num(key, v);
-  else if (key == "filter_frac") filter_frac = to_num(key, v);
-  else if (key == "pfx_h") {
-    pfx_h = (int)to_num(key, v);
-    if (pfx_h < 0 || pfx_h > 458752) fail("tuning: pfx_h must be in [0, 458752]");
-  }
-  else if (key == "tiles_w") {
-    tiles_w = (int)to_num(key, v);
-    if (tiles_w != 4 && tiles_w != 8 && tiles_w != 16) fail("tuning: tiles_w must be 4, 8 or 16");
-  }
-  else if (key == "dirs") {
-    for (char c : v)
-      if (c != 'T' && c != 'B' && c != '.') fail("tuning: dirs takes T, B or . per level");
-    dirs = v;
-  } else {
-    fail("tuning: unknown key '" + key +
-         "' (gamma gamma2 pfx codes code_deg lean lean_min lazy td_fused td_bm batch bu_max tiles tiles_code_deg full dskip push_after dskip3 chunk2 wide_few pfx_h filter_frac tiles_w dirs)");
-  }
-}
-
-void Tuning::parse(const std::string& spec) {
-  size_t p = 0;
-  while (p < spec.size()) {
-    size_t e = spec.find_first_of(",;", p);  // (';' too: shell tools split env lists at ',')
-    if (e == std::string::npos) e = spec.size();
-    const std::string kv = spec.substr(p, e - p);
-    p = e + 1;
-    if (kv.empty()) continue;
-    const size_t q = kv.find('=');
-    if (q == std::string::npos) fail("tuning: expected key=value, got '" + kv + "'");
-    set(kv.substr(0, q), kv.substr(q + 1));
-  }
-}
-
-const Tuning& Tuning::process_default() {
-  static const Tuning t = [] {
-    Tuning d;
-    if (const char* e = getenv("MSBFS_TUNE")) {
-      d.parse(e);
-      fprintf(stderr, "msbfs: MSBFS_TUNE=%s\n", e);  // never a silent algorithm change
-    }
-    return d;
-  }();
-  return t;
-}
 
 // ---- construction ----------------------------------------------------------------------------
 BitparSolver::BitparSolver(const DeviceGraph& g, int max_groups)
@@ -151,14 +67,9 @@ BitparSolver::BitparSolver(const DeviceGraph& g, int max_groups)
 void BitparSolver::run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
                        int64_t* edges2, RunStats* st, hipStream_t stream) {
   const int64_t builds0 = plen_builds_;
-  int64_t k0 = 0;
-  while (k0 < K) {
-    int64_t remain = K - k0;
-    int w = 1;
-    while (w * 64 < remain && w < std::min(maxW_, opt.max_words)) w <<= 1;
-    const int64_t nb = std::min<int64_t>(remain, 64 * w);
-    run_batch(w, k0, nb, qoff, qids, F + k0, edges2 ? edges2 + k0 : nullptr, st, stream);
-    k0 += nb;
+  const int mw = std::min(maxW_, opt.max_words);
+  for (Batch b = batch_at(K, 0, mw); b.k0 < K; b = batch_at(K, b.k0 + b.nb, mw)) {
+    run_batch(b.w, b.k0, b.nb, qoff, qids, F + b.k0, edges2 ? edges2 + b.k0 : nullptr, st, stream);
     if (st) st->batches++;
   }
   if (st) st->builds += plen_builds_ - builds0;
@@ -346,6 +257,7 @@ void BitparSolver::levels(Loop& S, RunStats* st, hipStream_t s) {
       rec.batch = (int32_t)st->batches;
       rec.level = (int32_t)S.level;
       rec.dir = bottom_up ? 'B' : 'T';
+      rec.kind = bottom_up ? S.kind : 0;
       rec.nf = S.nf;
       rec.ef = S.ef;
       rec.nf_next = (int64_t)c.fl2;
@@ -355,9 +267,9 @@ void BitparSolver::levels(Loop& S, RunStats* st, hipStream_t s) {
     }
     if (trace) {
       fprintf(stderr,
-              "[msbfs bp W=%d] level %u %s nf=%lld ef=%lld -> nf'=%lld ef'=%lld touched=%u "
+              "[msbfs bp W=%d] level %u %s%c nf=%lld ef=%lld -> nf'=%lld ef'=%lld touched=%u "
               "active=%lld (wide %lld) ea=%lld ev=%lld  %.3f ms\n",
-              W, S.level, bottom_up ? "BU" : "TD", (long long)S.nf, (long long)S.ef,
+              W, S.level, bottom_up ? "BU" : "TD", bottom_up ? S.kind : ' ', (long long)S.nf, (long long)S.ef,
               (long long)c.fl2, (long long)c.ef2, c.touched, (long long)S.na, (long long)S.nactw,
               (long long)S.ea, (long long)(S.ev + (long long)c.ev2), lms);
     }

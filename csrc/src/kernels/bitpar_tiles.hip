@@ -73,7 +73,6 @@ const BitparSolver::TileSet* BitparSolver::pfx_tiles(int W, int part, int nparts
     if (T.part == part && T.nparts == nparts) return &T;
     ++it;
   }
-  constexpr int32_t kPfxH = kTileHubW * 32;
   // prefix lengths at the tiles' bound: the cached ones when they are for this bound, else a
   // temporary copy, so that building another partition's tiles (prepare_hybrid) does not evict
   // the bound of the untiled prefix level that prepare_queries built
@@ -145,11 +144,7 @@ const BitparSolver::TileSet* BitparSolver::pfx_tiles(int W, int part, int nparts
   T.nparts = nparts;
   T.key[0] = g_.rowptr;
   T.key[1] = g_.col;
-  if (num_cus_ == 0) {
-    hipDeviceProp_t prop;
-    MSBFS_HIP_CHECK(hipGetDeviceProperties(&prop, g_.device));
-    num_cus_ = prop.multiProcessorCount;
-  }
+  (void)num_cus();
   fbm_tile_.ensure((size_t)((g_.n + 31) / 32 + 1) * sizeof(uint32_t));
   if (!zrow_.p) {
     zrow_.alloc(16 * sizeof(uint64_t));
@@ -210,7 +205,7 @@ int BitparSolver::tiles_pull(Loop& S, hipStream_t s, const uint64_t* R, uint64_t
   const int64_t nwords = (g_.n + 31) / 32;
   MSBFS_HIP_CHECK(hipMemsetAsync(fbm_tile_.p, 0, (size_t)nwords * sizeof(uint32_t), s));
   const uint32_t* pvis = snap ? snap : anyvis_.as<uint32_t>();
-  const int grid = std::max(1, num_cus_);
+  const int grid = std::max(1, num_cus());
   // tile ranges: one launch for the whole level, or one per own-vertex range of a chunked
   // hybrid phase A (each range's rows are final once its launch and, for the first, the big
   // vertices' finalize ran; on_chunk then packs and sends them while the next range computes)

@@ -91,7 +91,9 @@ class Solver:
 
     def level_trace(self) -> list:
         """Per-level records of the last run / hybrid phase (bit-parallel solver): batch, level,
-        dir ('T' push / 'B' pull), frontier size nf and degree sum ef entering the level, newly
+        dir ('T' push / 'B' pull), kind (which pull a 'B' level ran: 't' tiles, 'p' per-vertex
+        prefix, 'h' LDS-hub filtered, 'l' lean + overflow, 'f' full, 'n' plain narrow; '' for a
+        push), frontier size nf and degree sum ef entering the level, newly
         visited vertices nf_next, active (bottom-up) or touched (top-down) vertices, host ms."""
         L = native.lib()
         n = int(L.msbfs_solver_levels(self._h, None, 0))

@@ -47,11 +47,12 @@ class Stats(C.Structure):
 class Level(C.Structure):
     """One BFS level of a solver run (msbfs_level in msbfs.h)."""
     _fields_ = [("batch", C.c_int32), ("level", C.c_int32), ("dir", C.c_char),
-                ("pad", C.c_char * 3), ("nf", C.c_int64), ("ef", C.c_int64),
+                ("kind", C.c_char), ("pad", C.c_char * 2), ("nf", C.c_int64), ("ef", C.c_int64),
                 ("nf_next", C.c_int64), ("active", C.c_int64), ("ms", C.c_double)]
 
     def as_dict(self):
         return {"batch": self.batch, "level": self.level, "dir": self.dir.decode(),
+                "kind": self.kind.decode().strip("\0"),  # (pull levels; "" for a push level)
                 "nf": self.nf, "ef": self.ef, "nf_next": self.nf_next, "active": self.active,
                 "ms": self.ms}
 

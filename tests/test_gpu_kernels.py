@@ -277,6 +277,8 @@ def test_bitpar_prefix_pull_tail_push(msbfs_pkg):
             out[pfx] = s.run(qs).F
             tr = s.level_trace()
         assert tr[0]["dir"] == "T" and tr[1]["dir"] == "B"  # the prefix level is level 2
+        # 16 words: over the tiles; without the prefix pull whole rows, LDS-hub filtered
+        assert tr[0]["kind"] == "" and tr[1]["kind"] == ("t" if pfx == "2" else "h"), (pfx, tr[1])
     assert np.array_equal(out["2"], out["0"])
     sub = qs.subset(np.arange(0, 1024, 128))
     with m.Solver(g, "dist") as ds:
@@ -308,6 +310,8 @@ def test_bitpar_prefix_bound(msbfs_pkg, K):
             out[name + "2"] = s.run(qs).F
             tr = s.level_trace()
         assert "".join(t["dir"] for t in tr).startswith("TBT" if "td3" in name else "TB"), name
+        # level 2 ran the per-vertex prefix pull (without it: whole rows, LDS-hub filtered)
+        assert tr[1]["level"] == 2 and tr[1]["kind"] == ("h" if name == "off" else "p"), (name, tr[1])
     for name in out:
         assert np.array_equal(out[name], out["off"]), name
     sub = qs.subset(np.arange(0, K, 7))
@@ -344,6 +348,11 @@ def test_bitpar_tiled_first_pull(msbfs_pkg, K):
             out[name + "2"] = s.run(qs).F  # reuse: the acc rows and stamps were left clean
             tr = s.level_trace()
         assert "".join(t["dir"] for t in tr).startswith("TBT" if "td3" in name else "TB")
+        # level 2 ran over the tiles wherever they are on for this word count (from tiles_w = 8
+        # words on by default: K = 200 is 4 words), else the per-vertex prefix pull
+        words = 16 if K > 512 else 8 if K > 256 else 4
+        tiled = tun.get("tiles", 1) and words >= tun.get("tiles_w", 8)
+        assert tr[1]["level"] == 2 and tr[1]["kind"] == ("t" if tiled else "p"), (name, tr[1])
     for name in out:
         assert np.array_equal(out[name], out["plain"]), name
     sub = qs.subset(np.arange(0, K, 97))
@@ -417,14 +426,21 @@ def test_bitpar_lean_and_lazy_paths(msbfs_pkg, knobs):
     cases = [(dg, hg, 1024), (dg, hg, 2100), (dg, hg, 128)]
     for name, g in _graphs(m)[2:4]:
         cases.append((g.to_device(0), g, 300))
+    kinds = []  # of every level, per case
     for dev, host, K in cases:
         qs = m.QuerySet.random(host.n, K, 8, seed=K + 1)
         ref = m.cpu_bfs(host, qs)
         with m.Solver(dev, "bitpar", max_groups=min(K, 1024), tuning=knobs) as s:
             r = s.run(qs)
             r2 = s.run(qs)
+            kinds.append("".join(t["kind"] for t in s.level_trace()))
         assert np.array_equal(r.F, ref.F), (knobs, K)
         assert np.array_equal(r2.F, ref.F), (knobs, K)
+    # the lean pass really ran on the RMAT (third pull level on, unfiltered), or never
+    if knobs.get("lean_min") == 0:
+        assert any("l" in k for k in kinds[:3]), kinds
+    if knobs.get("lean") == 0:
+        assert not any("l" in k for k in kinds), kinds
 
 
 @pytest.mark.parametrize("tun", [{"bu_max": 1 << 30}, {"bu_max": 1 << 30, "batch": 2},
@@ -672,6 +688,8 @@ def test_bitpar_done_rows_skipped(msbfs_pkg, dirs, extra):
             with m.Solver(dev, "bitpar", max_groups=min(K, 1024), tuning=tun) as s:
                 assert np.array_equal(s.run(qs).F, ref.F), (dirs, extra, K, dskip)
                 assert np.array_equal(s.run(qs).F, ref.F), (dirs, extra, K, dskip)
+                if extra.get("full") == 0:  # (the per-vertex pulls only)
+                    assert not any(t["kind"] == "f" for t in s.level_trace()), (dirs, K, dskip)
 
 
 def test_prepare_queries_builds_prefix_lengths(msbfs_pkg):
