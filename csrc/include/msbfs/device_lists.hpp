@@ -100,6 +100,20 @@ __device__ __forceinline__ void block_sum_add(unsigned long long val, unsigned l
   }
 }
 
+// 32-bit block sum, one atomic per block
+__device__ __forceinline__ void block_sum_add32(uint32_t val, uint32_t* dst, uint32_t* scratch) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) val += __shfl_xor(val, off);
+  __syncthreads();
+  if (lane_id() == 0) scratch[threadIdx.x >> 6] = val;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += scratch[w];
+    if (t) atomicAdd(dst, t);
+  }
+}
+
 // Device counters; every field on its own 128-B line so unrelated atomics never share a line.
 struct alignas(128) Slot32 {
   uint32_t v;

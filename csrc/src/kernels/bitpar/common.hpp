@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "bits.hpp"
 #include "msbfs/device.hpp"
 #include "msbfs/device_lists.hpp"
 
@@ -105,11 +106,6 @@ __device__ __forceinline__ void wq_flush_block(int32_t* q, uint32_t& n, int32_t*
 }
 
 template <int VW>
-struct V {
-  uint64_t w[VW];
-};
-
-template <int VW>
 __device__ __forceinline__ V<VW> ldv(const uint64_t* p) {
   V<VW> r;
   if constexpr (VW == 2) {
@@ -134,14 +130,6 @@ __device__ __forceinline__ void stv(uint64_t* p, const V<VW>& v) {
     *p = v.w[0];
   }
 }
-template <int VW>
-__device__ __forceinline__ V<VW> vzero() {
-  V<VW> r;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) r.w[j] = 0;
-  return r;
-}
-
 // Wave-uniform copies (SGPRs) of values every lane holds identically: keeps loops over them
 // uniform (scalar branches) instead of exec-masked "divergent" loops.
 __device__ __forceinline__ int64_t uni64(int64_t x) {
@@ -214,6 +202,108 @@ __device__ __forceinline__ bool any_visited(const uint32_t* anyvis, int32_t u) {
   return (anyvis[u >> 5] >> (u & 31)) & 1u;
 }
 
+// the alive groups of the batch on lane slot `slot` (alive mask & the batch's group mask)
+template <int VW>
+__device__ __forceinline__ V<VW> alive_mask(const uint64_t* alive, const uint64_t* gmask, int slot) {
+  V<VW> am;
+#pragma unroll
+  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  return am;
+}
+// A vertex's own slice R[off ..] under a snapshot of the any-visited bitmap (nullptr: none): a
+// vertex the snapshot does not mark has an all-zero row by definition, whatever the buffer holds
+// (rows of never-visited vertices may be stale, see k_zero_part_rows)
+template <int VW>
+__device__ __forceinline__ V<VW> own_row(const uint64_t* R, const uint32_t* snap, int32_t v,
+                                         int64_t off) {
+  return (snap && !any_visited(snap, v)) ? vzero<VW>() : ldv<VW>(R + off);
+}
+
+// The end of a pull / finalize tile for the vertex of this lane group (whole wave, uniform
+// control flow): from the lanes' new-bits flags, the vertex's done bit (no alive group left), its
+// any-visited bit (first visit) and the three degree sums (eu: vertices staying active, only
+// with count_eu; ef: the new frontier; ev: first visits). keep / app: the group's leader lane
+// keeps the vertex active / appends it to the new frontier; nf: the group is not full (every
+// lane of it). COMBINE: see wave_set_bits.
+struct Settled {
+  bool keep, app, nf;
+};
+template <int W, bool COMBINE>
+__device__ __forceinline__ Settled settle_vertex(bool valid, int32_t v, uint32_t deg,
+                                                 const NewBits<Lay<W>::VW>& bits, uint32_t* done,
+                                                 uint32_t* anyvis, unsigned long long& eu,
+                                                 unsigned long long& ef, unsigned long long& ev,
+                                                 bool count_eu = true) {
+  using L = Lay<W>;
+  constexpr int G = L::G;
+  const int lane = lane_id(), slot = lane % G, sub = lane / G;
+  const uint64_t bn = __ballot(bits.anynew), bf = __ballot(bits.notfull);
+  const bool g_new = (bn >> (sub * G)) & L::GBITS;
+  const bool g_nf = (bf >> (sub * G)) & L::GBITS;
+  const bool leader = valid && slot == 0;
+  wave_set_bits<COMBINE>(done, v, leader && !g_nf);
+  const bool keep = leader && g_nf, app = leader && g_new;
+  if (keep && count_eu) eu += deg;
+  if (app) ef += deg;
+  {
+    const bool g_first = g_new && !((__ballot(bits.rnz) >> (sub * G)) & L::GBITS);
+    wave_set_bits<COMBINE>(anyvis, v, leader && g_first);
+    if (leader && g_first) ev += deg;
+  }
+  return {keep, app, g_nf};
+}
+
+// chunk pulls: OR the partial rows of the wave's lane groups (G lanes each) together
+template <int VW, int G>
+__device__ __forceinline__ void or_across_groups(V<VW>& a) {
+#pragma unroll
+  for (int off = G; off < 64; off <<= 1)
+#pragma unroll
+    for (int j = 0; j < VW; ++j) a.w[j] |= __shfl_xor(a.w[j], off);
+}
+// ... and whether a, with the bits g others published, covers every missing alive group unv on
+// every lane of the wave
+template <int VW>
+__device__ __forceinline__ bool covers(const V<VW>& a, const V<VW>& g, const V<VW>& unv) {
+  bool cov = true;
+#pragma unroll
+  for (int j = 0; j < VW; ++j) cov &= ((a.w[j] | g.w[j]) & unv.w[j]) == unv.w[j];
+  return !__ballot(!cov);
+}
+// phase B of the chunk pulls: the lane groups OR the rows of the ids lst[b ..], PB per group per
+// call (lane group `sub` takes entries b + q * S + sub), into a. CLAMP: idle lanes read list
+// entry 0 instead of branching around the LDS read; either way they load no row (their address
+// costs the address unit as much as a row).
+template <int W, int PB, bool CLAMP>
+__device__ __forceinline__ void gather_rows(const int32_t* lst, int cnt, int b, const uint64_t* R,
+                                            V<Lay<W>::VW>& a) {
+  using L = Lay<W>;
+  constexpr int VW = L::VW, G = L::G, S = L::VPW;
+  const int lane = lane_id(), slot = lane % G, sub = lane / G;
+  int32_t uu[PB];
+#pragma unroll
+  for (int q = 0; q < PB; ++q) {
+    const int k = b + q * S + sub;
+    if constexpr (CLAMP) {
+      const int32_t x = lst[k < cnt ? k : 0];
+      uu[q] = k < cnt ? x : -1;
+    } else {
+      uu[q] = k < cnt ? lst[k] : -1;
+    }
+  }
+  // loads first, ORs after: the compiler then keeps all PB loads in flight
+  V<VW> x[PB];
+#pragma unroll
+  for (int q = 0; q < PB; ++q) {
+    x[q] = vzero<VW>();
+    if (uu[q] >= 0) x[q] = ldv<VW>(R + (int64_t)uu[q] * W + slot * VW);
+  }
+#pragma unroll
+  for (int q = 0; q < PB; ++q)
+#pragma unroll
+    for (int j = 0; j < VW; ++j) a.w[j] |= x[q].w[j];
+}
+
 // ---- per-group level counters in LDS ------------------------------------------------------------
 template <int W, bool COUNT>
 struct Lds {
@@ -259,106 +349,118 @@ __device__ __forceinline__ void slab_store(Lds<W, COUNT>& s, uint32_t* slabF,
   }
 }
 
-// Register-resident bit-sliced (carry-save) counters: bit b of c[j][d] is bit d of the count of
-// group (slot*VW + j)*64 + b. Adding a 64-bit new-bits word costs 2*D branch-free ops, vs one
-// LDS atomic per set bit in a divergent loop. Spilled to LDS every < 2^D additions.
-template <int VW, int DD = 6>
-struct BitCounter {
-  static constexpr int D = DD;
-  uint64_t c[VW][D];
-  __device__ __forceinline__ void zero() {
+// The spills of the register bit-sliced group counters (BitCounter, bits.hpp) into LDS counter
+// rows: one LDS add per counter bit with a non-zero count; the counter is zero afterwards.
+template <int VW, int D>
+__device__ __forceinline__ void spill(BitCounter<VW, D>& bc, uint32_t* f, int slot) {
 #pragma unroll
-    for (int j = 0; j < VW; ++j)
-#pragma unroll
-      for (int d = 0; d < D; ++d) c[j][d] = 0;
+  for (int j = 0; j < VW; ++j) {
+    uint64_t any = bc.any(j);
+    const int base = (slot * VW + j) * 64;
+    while (any) {
+      const int b = __ffsll((unsigned long long)any) - 1;
+      any &= any - 1;
+      atomicAdd(&f[base + b], bc.count(j, b));
+    }
   }
-  __device__ __forceinline__ void add(const V<VW>& x) {
+  bc.zero();
+}
+// Same, into rows of STRIDE words per 64 groups. STRIDE = 65 skews the groups of different
+// lane slots onto different LDS banks: with 64 every lane of the wave hit the bank of bit b
+// (level-3 k_bu_narrow counted ~5e8 bank-conflict cycles; RMAT-26 levels 3 / 4 6.46 / 2.53 ->
+// 6.22 / 2.46 ms with 65). Summing the sub-groups' counts with shuffles before one atomic per
+// slot measured slower (a 64-step wave-uniform bit loop: 27.2 ms/step).
+template <int STRIDE, int VW, int D>
+__device__ __forceinline__ void spill_strided(BitCounter<VW, D>& bc, uint32_t* f, int slot) {
 #pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      uint64_t carry = x.w[j];
+  for (int j = 0; j < VW; ++j) {
+    // (any() / count() written out: through them k_td_fused and k_bu_wide_finalize at one word
+    // took one more VGPR)
+    uint64_t any = 0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) any |= bc.c[j][d];
+    const int base = (slot * VW + j) * STRIDE;
+    while (any) {
+      const int b = __ffsll((unsigned long long)any) - 1;
+      any &= any - 1;
+      uint32_t v = 0;
+#pragma unroll
+      for (int d = 0; d < D; ++d) v |= (uint32_t)((bc.c[j][d] >> b) & 1ull) << d;
+      atomicAdd(&f[base + b], v);
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) bc.c[j][d] = 0;
+  }
+}
+// spill_strided with 32-bit halves (~12 instead of ~21 VALU per set counter bit: the
+// first pull level sets about half the bits of every word between two spills). It slices the
+// counter words itself: count() shifts 64-bit words.
+template <int STRIDE, int VW, int D>
+__device__ __forceinline__ void spill_strided32(BitCounter<VW, D>& bc, uint32_t* f, int slot) {
+#pragma unroll
+  for (int j = 0; j < VW; ++j) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      uint32_t sl[D], any = 0;
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        const uint64_t t = c[j][d] & carry;
-        c[j][d] ^= carry;
-        carry = t;
+        sl[d] = (uint32_t)(bc.c[j][d] >> (32 * h));
+        any |= sl[d];
       }
-    }
-  }
-  template <int W, bool COUNT>
-  __device__ __forceinline__ void spill(Lds<W, COUNT>& s, int slot) {
-    spill(s.f, slot);
-  }
-  __device__ __forceinline__ void spill(uint32_t* f, int slot) {
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      uint64_t any = 0;
-#pragma unroll
-      for (int d = 0; d < D; ++d) any |= c[j][d];
-      const int base = (slot * VW + j) * 64;
+      uint32_t* row = f + (slot * VW + j) * STRIDE + 32 * h;
       while (any) {
-        const int b = __ffsll((unsigned long long)any) - 1;
+        const int b = __ffs(any) - 1;
         any &= any - 1;
         uint32_t v = 0;
 #pragma unroll
-        for (int d = 0; d < D; ++d) v |= (uint32_t)((c[j][d] >> b) & 1ull) << d;
-        atomicAdd(&f[base + b], v);
+        for (int d = 0; d < D; ++d) v |= ((sl[d] >> b) & 1u) << d;
+        atomicAdd(&row[b], v);
       }
+    }
 #pragma unroll
-      for (int d = 0; d < D; ++d) c[j][d] = 0;
+    for (int d = 0; d < D; ++d) bc.c[j][d] = 0;
+  }
+}
+
+// The fused per-group counts of a level kernel: every lane adds its slice's new bits to register
+// counters, which spill into the block's LDS counter rows (lds: CR * W words, CR words per 64
+// groups; 65 = bank-skewed, see spill_strided) every 2^D - 1 adds; at the end the rows go to this
+// block's row of the level's counter slab (plain stores, summed by k_level_reduce). HALVES: the
+// spill works on 32-bit halves (spill_strided32). CR, D and HALVES are measured choices of each
+// kernel (see the comments at their GroupCounts).
+template <int W, int D, int CR, bool HALVES>
+struct GroupCounts {
+  static constexpr int VW = Lay<W>::VW;
+  static constexpr int kLdsWords = CR * W;
+  static_assert(CR == 64 || CR == 65, "plain or bank-skewed rows");
+  uint32_t* cnt;
+  BitCounter<VW, D> bc;
+  int nadd, slot;
+  __device__ __forceinline__ GroupCounts(uint32_t* lds, int lane_slot) : cnt(lds), slot(lane_slot) {}
+  // before the block's first barrier (nthreads = the block size)
+  __device__ __forceinline__ void zero(int nthreads) {
+    for (int i = threadIdx.x; i < CR * W; i += nthreads) cnt[i] = 0;
+    bc.zero();
+    nadd = 0;
+  }
+  __device__ __forceinline__ void spill_now() {
+    if constexpr (HALVES) spill_strided32<CR>(bc, cnt, slot);
+    else spill_strided<CR>(bc, cnt, slot);
+  }
+  // every lane of the block, once per tile (nw is zero for lanes without a vertex)
+  __device__ __forceinline__ void add(const V<VW>& nw) {
+    bc.add(nw);
+    if (++nadd == (1 << D) - 1) {
+      spill_now();
+      nadd = 0;
     }
   }
-  // Same, into rows of STRIDE words per 64 groups. STRIDE = 65 skews the groups of different
-  // lane slots onto different LDS banks: with 64 every lane of the wave hit the bank of bit b
-  // (level-3 k_bu_narrow counted ~5e8 bank-conflict cycles; RMAT-26 levels 3 / 4 6.46 / 2.53 ->
-  // 6.22 / 2.46 ms with 65). Summing the sub-groups' counts with shuffles before one atomic per
-  // slot measured slower (a 64-step wave-uniform bit loop: 27.2 ms/step).
-  template <int STRIDE>
-  __device__ __forceinline__ void spill_strided(uint32_t* f, int slot) {
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      uint64_t any = 0;
-#pragma unroll
-      for (int d = 0; d < D; ++d) any |= c[j][d];
-      const int base = (slot * VW + j) * STRIDE;
-      while (any) {
-        const int b = __ffsll((unsigned long long)any) - 1;
-        any &= any - 1;
-        uint32_t v = 0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) v |= (uint32_t)((c[j][d] >> b) & 1ull) << d;
-        atomicAdd(&f[base + b], v);
-      }
-#pragma unroll
-      for (int d = 0; d < D; ++d) c[j][d] = 0;
-    }
-  }
-  // spill_strided with 32-bit halves (~12 instead of ~21 VALU per set counter bit: the
-  // first pull level sets about half the bits of every word between two spills)
-  template <int STRIDE>
-  __device__ __forceinline__ void spill_strided32(uint32_t* f, int slot) {
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        uint32_t sl[D], any = 0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          sl[d] = (uint32_t)(c[j][d] >> (32 * h));
-          any |= sl[d];
-        }
-        uint32_t* row = f + (slot * VW + j) * STRIDE + 32 * h;
-        while (any) {
-          const int b = __ffs(any) - 1;
-          any &= any - 1;
-          uint32_t v = 0;
-#pragma unroll
-          for (int d = 0; d < D; ++d) v |= ((sl[d] >> b) & 1u) << d;
-          atomicAdd(&row[b], v);
-        }
-      }
-#pragma unroll
-      for (int d = 0; d < D; ++d) c[j][d] = 0;
-    }
+  // block-uniform, at the kernel's end: slab row blockIdx.x of the rows starting at slabF
+  __device__ __forceinline__ void store(uint32_t* slabF, int nthreads) {
+    spill_now();
+    __syncthreads();
+    uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
+    for (int i = threadIdx.x; i < 64 * W; i += nthreads) row[i] = cnt[CR == 65 ? i + (i >> 6) : i];
   }
 };
 
@@ -506,12 +608,12 @@ __global__ __launch_bounds__(kBlock) void k_count_frontier(const int32_t* fl, co
     } else {
       bc.add(nw);
       if (++nadd == (1 << BitCounter<VW>::D) - 1) {
-        bc.spill(s, slot);
+        spill(bc, s.f, slot);
         nadd = 0;
       }
     }
   }
-  if constexpr (!COUNT) bc.spill(s, slot);
+  if constexpr (!COUNT) spill(bc, s.f, slot);
   slab_store<W, COUNT>(s, slabF, slabE);
 }
 

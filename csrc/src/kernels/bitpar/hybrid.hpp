@@ -269,9 +269,7 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_setup(const uint64_t* recv, i
   unsigned long long eu = 0;
   const int64_t nwords32 = (n_eff + 31) / 32;
   const int lane = lane_id(), slot = lane % G, sub = lane / G, wv = threadIdx.x >> 6;
-  V<VW> am;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  const V<VW> am = alive_mask<VW>(alive, gmask, slot);
   for (int64_t tb = (int64_t)blockIdx.x * TILE; tb < n_eff; tb += (int64_t)gridDim.x * TILE) {
     const int64_t v = tb + wv * VPW + sub;
     V<VW> x = vzero<VW>();

@@ -1,353 +1,22 @@
-// Bit-parallel MS-BFS: bottom-up (pull) level kernels — active lists, sparse row codes, prefix
-// pull + tail push, the narrow lane-group pull, the lean first-row pass, hub edge chunks and the
-// wide finalize.
+// Bit-parallel MS-BFS: bottom-up (pull) level kernels — the narrow lane-group pull, the lean
+// first-row pass, hub edge chunks and the wide finalize. The list kernels: pull_lists.hpp; sparse
+// row codes and the tail push: pull_tail.hpp.
 #pragma once
 
 #include "common.hpp"
+#include "pull_lists.hpp"
+#include "pull_plan.hpp"
+#include "pull_tail.hpp"
 
 namespace msbfs {
 namespace bp {
-
-// build the bottom-up active lists (deg > 0, not done) over the vertices v = part + i*nparts,
-// i < cnt, split by degree, or by the row prefix length plen[v] when given (the untiled prefix
-// level pulls only the prefix: a vertex of high degree with a short prefix is a narrow one)
-// (nparts = 1: every vertex; the hybrid mode's vertex-partitioned level pulls only for its own
-// residue class)
-template <int QCAP>
-__global__ __launch_bounds__(kBlock) void k_build_active(int64_t cnt, int part, int nparts,
-                                                         const int64_t* rowptr,
-                                                         const uint32_t* done, int wide_deg,
-                                                         int32_t* act, int32_t* actw, Ctr* ctr,
-                                                         const int32_t* plen = nullptr,
-                                                         int64_t n_eff = -1) {
-  // n_eff >= 0 (with plen, degree-relabelled rows: exactly the vertices < n_eff have edges): no
-  // row offsets are read at all (RMAT-30: 8.6 GB), and eu2 stays 0 (its caller reads only the
-  // list sizes)
-  // Each block owns QCAP consecutive list positions j and flushes its narrow queue once at the
-  // end (one counter atomic per QCAP vertices: atomics on one address serialise, and 64K of them
-  // were most of this kernel's time on 33M vertices). Blocks are dispatched in order, so the
-  // lists come out nearly ascending (hubs first in the wide list: the chunk kernel deals chunks
-  // in list order, and a grid-stride build that interleaved distant ranges cost ~1 ms of level-2
-  // tail on RMAT-26). The rare wide vertices go through a small queue flushed when needed.
-  constexpr int VPT = 4;  // vertices per thread per step (loads first, pushes after)
-  constexpr int64_t kStep = (int64_t)VPT * kBlock;
-  static_assert(QCAP % kStep == 0, "whole steps per block");
-  __shared__ LdsQueueN<QCAP> qn;
-  __shared__ LdsQueue qw;
-  __shared__ unsigned long long scratch[kWaves];
-  q_init(qn);
-  q_init(qw);
-  __syncthreads();
-  unsigned long long eu = 0;
-  const int64_t b0 = (int64_t)blockIdx.x * QCAP, b1 = min(b0 + (int64_t)QCAP, cnt);
-  for (int64_t b = b0; b < b1; b += kStep) {
-    int64_t d[VPT], sd[VPT];
-    uint32_t dw[VPT];
-#pragma unroll
-    for (int q = 0; q < VPT; ++q) {
-      const int64_t j = b + q * kBlock + threadIdx.x;
-      const int64_t i = part + j * nparts;
-      d[q] = 0;
-      sd[q] = 0;
-      dw[q] = ~0u;
-      if (j < b1) {
-        if (n_eff >= 0) {
-          d[q] = i < n_eff ? 1 : 0;
-          if (i < n_eff) sd[q] = (int64_t)plen[i];
-        } else {
-          d[q] = rowptr[i + 1] - rowptr[i];
-          sd[q] = plen ? (int64_t)plen[i] : d[q];
-        }
-        dw[q] = done[i >> 5];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < VPT; ++q) {
-      const int64_t i = part + (b + q * kBlock + threadIdx.x) * nparts;
-      const bool ok = d[q] > 0 && !((dw[q] >> (i & 31)) & 1u);
-      if (ok && n_eff < 0) eu += (unsigned long long)d[q];
-      q_push(qn, ok && sd[q] <= wide_deg, (int32_t)i);
-      q_push(qw, ok && sd[q] > wide_deg, (int32_t)i);
-    }
-    q_flush(qw, actw, &ctr->actw2.v, (int)kStep, false);
-  }
-  q_flush(qn, act, &ctr->act2.v, 0, true);
-  q_flush(qw, actw, &ctr->actw2.v, 0, true);
-  block_sum_add(eu, &ctr->eu2.v, scratch);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Sparse row codes for the first bottom-up level. Its frontier is the level-1 frontier: outside
-// the top hubs a vertex there was reached from one or two sources, so its visited row (8*W bytes)
-// mostly holds a single set bit (RMAT-26, 1024 groups: ~1.2 bits per row below degree ~9K).
-// Gathering those rows made the level bound by Infinity-Cache traffic (rocprofv3, k_bu_chunks at
-// level 2: 44 % L2 hit rate, ~115 GB of L2 misses for 0.74e9 row gathers). code[u] (32 bit):
-// 0 = row empty; else bits 30-31 = number of set groups c (1-3) and bits 10*i .. 10*i+9 their
-// ids (groups < 1024); kDenseCode = anything else (gathered as before). Several slots: the
-// multi-bit rows of the mid-degree ids (RMAT-26: degree 1K-8K, 1-2 expected bits) were most of
-// the level's L2 misses (the dense rows left did not fit one XCD's 4 MB L2 next to the top hubs'
-// rows; single-slot codes 7.5 ms for the level's chunk pulls, two slots 6.9 ms). The
-// frontier's codes occupy a 64x smaller footprint than its rows, so the pulls mostly hit L2.
-// Only ids >= code_from use codes: after degree relabelling the lower ids are the hubs, whose rows
-// are dense and L2-resident. The codes live in the top-down touched buffer (unused by bottom-up
-// levels, rebuilt by every top-down level).
-// ---------------------------------------------------------------------------------------------
-constexpr uint32_t kDenseCode = 0xFFFFFFFFu;  // (3 slots of group 1023: never a real code)
-constexpr int kCodeSlots = 3;
-// group of slot i of a sparse code, -1 for an unused slot
-__device__ __forceinline__ int code_g(uint32_t c, int i) {
-  return i < (int)(c >> 30) ? (int)((c >> (10 * i)) & 1023u) : -1;
-}
-constexpr int32_t kNoCodes = INT32_MAX;
-
-template <int W>
-// ids [lo, hi), then the list entries fl[0..nl) >= hi
-__global__ __launch_bounds__(kBlock) void k_build_codes(const uint64_t* R, const uint32_t* anyvis,
-                                                        int64_t lo, int64_t hi, const int32_t* fl,
-                                                        int64_t nl, uint32_t* code) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < hi - lo + nl;
-       i += (int64_t)gridDim.x * kBlock) {
-    const int64_t u = i < hi - lo ? lo + i : (int64_t)fl[i - (hi - lo)];
-    if (i >= hi - lo && u < hi) continue;
-    uint32_t c = 0;
-    if (any_visited(anyvis, (int32_t)u)) {
-      int pc = 0;
-#pragma unroll
-      for (int j = 0; j < W; ++j) {
-        uint64_t w = R[u * W + j];
-        const int pw = __popcll(w);
-        if (pc + pw <= kCodeSlots) {  // (dense hub rows skip the bit loop)
-          while (w) {
-            const int b = __ffsll((unsigned long long)w) - 1;
-            w &= w - 1;
-            c |= (uint32_t)(j * 64 + b) << (10 * pc);
-            ++pc;
-          }
-        } else {
-          pc += pw;
-        }
-      }
-      c = pc == 0 ? 0u : pc <= kCodeSlots ? c | ((uint32_t)pc << 30) : kDenseCode;
-    }
-    code[u] = c;
-  }
-}
-
-// first id with degree < 2^k for k = 0..kDegBounds-1 (rows relabelled by descending degree: one
-// binary search per k, one thread each)
-constexpr int kDegBounds = 41;
-static __global__ void k_degree_bounds(const int64_t* rowptr, int64_t n, int32_t* out) {
-  const int k = threadIdx.x;
-  if (k >= kDegBounds) return;
-  const int64_t min_deg = (int64_t)1 << k;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (rowptr[mid + 1] - rowptr[mid] < min_deg) hi = mid;
-    else lo = mid + 1;
-  }
-  out[k] = (int32_t)lo;
-}
-
-// number of vertices with degree > d (bounds the wide list of any pull level)
-static __global__ __launch_bounds__(kBlock) void k_count_wide(const int64_t* rowptr, int64_t n, int64_t d,
-                                                       unsigned long long* out) {
-  __shared__ unsigned long long scratch[kWaves];
-  unsigned long long c = 0;
-  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n;
-       v += (int64_t)gridDim.x * kBlock)
-    c += rowptr[v + 1] - rowptr[v] > d;
-  block_sum_add(c, out, scratch);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Prefix pull + tail push for the first bottom-up level (rows sorted by id, degree relabelled).
-// The LDS hub bitmap covers the ids < H; a pull that scanned whole rows had to probe the global
-// visited bitmap for every neighbour id >= H (the degree tail: ~40 % of the edge endpoints on
-// RMAT-26, almost none of them in the level-1 frontier). Instead the pulls stop at the first id
-// >= H, and the few level-1 frontier vertices u >= H push their bits to their neighbours here:
-// acc[v] |= row(u) (atomicOr, mostly one word thanks to the sparse codes) and stamp[v] = epoch
-// (stamp = nullptr: the consumer reads every vertex's acc row instead).
-// The narrow pull folds acc[v] of stamped vertices into its accumulator (and clears it); wide
-// vertices collect it with their chunk results in k_bu_wide_finalize. Sources need no push:
-// every neighbour of a source was reached at level 1. Only own vertices (v % nparts == part) are
-// targets (the hybrid mode's level 2 pulls only those), and done vertices are skipped, so every
-// written acc entry is consumed and cleared within the level.
-// ---------------------------------------------------------------------------------------------
-template <int W>
-__global__ __launch_bounds__(kBlock) void k_push_tail(
-    const int32_t* fl, int64_t nf, int32_t H, const int64_t* rowptr, const int32_t* col,
-    const uint64_t* R, const uint32_t* code, int32_t code_from, const uint32_t* done,
-    int part, int nparts, uint64_t* acc, int32_t* stamp, int32_t epoch, int split) {
-  constexpr int PG = 64;  // lanes per wave: an entry's lanes take consecutive row entries
-  // `split` waves per frontier entry (wave s of entry i takes row entries s*64 + lane, step
-  // split*64; the host splits small frontiers only), UN entries per lane in flight: a frontier
-  // vertex of degree 30K otherwise kept one wave busy for ~470 dependent rounds of column id ->
-  // done probe -> atomic while the rest of the grid had finished (RMAT-30 / 32 groups: ~10K
-  // frontier vertices push; 1024 groups: ~100K+, mostly of low degree, one wave each)
-  constexpr int UN = 4;
-  const int SPLIT = split;
-  // own targets: v % nparts == part (hybrid phase A); a power-of-two count tests the low bits
-  // instead of dividing (v % nparts: ~40 VALU per neighbour entry)
-  const uint32_t pmask = (nparts & (nparts - 1)) == 0 ? (uint32_t)(nparts - 1) : 0u;
-  const int lane = lane_id();
-  const int64_t wave = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / PG;
-  const int64_t nwave = ((int64_t)gridDim.x * kBlock) / PG;
-  for (int64_t wi = wave; wi < nf * SPLIT; wi += nwave) {
-    const int64_t i = wi / SPLIT;
-    const int sp = (int)(wi % SPLIT);
-    const int32_t u = fl[i];
-    if (u < H) continue;
-    const uint32_t c = (code && u >= code_from) ? code[u] : kDenseCode;
-    if (c == 0) continue;
-    const int64_t b = rowptr[u], e = rowptr[u + 1];
-    const int64_t kStep = (int64_t)SPLIT * PG;
-    for (int64_t k0 = b + sp * PG + lane; k0 < e; k0 += UN * kStep) {
-      int32_t v[UN];
-      bool ok[UN];
-#pragma unroll
-      for (int q = 0; q < UN; ++q) {  // loads first (clamped index), tests after
-        const int64_t k = k0 + q * kStep;
-        const int32_t x = col[k < e ? k : k0];
-        v[q] = x;
-        ok[q] = k < e;
-      }
-#pragma unroll
-      for (int q = 0; q < UN; ++q)
-        if (nparts > 1)
-          ok[q] = ok[q] && (pmask ? ((uint32_t)v[q] & pmask) == (uint32_t)part
-                                  : v[q] % nparts == part);
-      if (done) {  // (nullptr: the consumer clears done rows too)
-        uint32_t dw[UN];
-#pragma unroll
-        for (int q = 0; q < UN; ++q) dw[q] = done[v[q] >> 5];
-#pragma unroll
-        for (int q = 0; q < UN; ++q) ok[q] = ok[q] && !((dw[q] >> (v[q] & 31)) & 1u);
-      }
-#pragma unroll
-      for (int q = 0; q < UN; ++q) {
-        if (!ok[q]) continue;
-        if (c != kDenseCode) {
-          for (int s = 0; s < kCodeSlots; ++s) {
-            const int g = code_g(c, s);
-            if (g >= 0)
-              atomicOr((unsigned long long*)&acc[(int64_t)v[q] * W + (g >> 6)], 1ull << (g & 63));
-          }
-        } else {
-          for (int j = 0; j < W; ++j) {
-            const uint64_t w = R[(int64_t)u * W + j];
-            if (w)
-              atomicOr((unsigned long long*)&acc[(int64_t)v[q] * W + j], (unsigned long long)w);
-          }
-        }
-        if (stamp) stamp[v[q]] = epoch;  // (nullptr: the consumer reads every acc row)
-      }
-    }
-  }
-}
-
-// 32-bit block sum, one atomic per block
-__device__ __forceinline__ void block_sum_add32(uint32_t val, uint32_t* dst, uint32_t* scratch) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) val += __shfl_xor(val, off);
-  __syncthreads();
-  if (lane_id() == 0) scratch[threadIdx.x >> 6] = val;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += scratch[w];
-    if (t) atomicAdd(dst, t);
-  }
-}
-
-// The tail push AFTER the tiled prefix pull (tuning key push_after; one GPU, no chunked
-// exchange): the pushed bits go straight into the level's output rows O, so the tile epilogue
-// reads no acc row (4.2 GB on RMAT-26 / 1024 groups, every tile vertex) and a push whose bit
-// the prefix pull already set costs a plain load instead of an atomic. The push then does the
-// accounting of what it adds (the epilogue has run): per-group counts of the bits its
-// atomicOr newly set (LDS counters -> this block's slab row), and for a vertex it gave its
-// first new bit of the level, the frontier bit (+ count, degree sum), and for one it gave its
-// first bit at all, the any-visited bit (+ degree sum). A vertex the pushed bits complete is
-// left not done (the next pull finds it covered). Census (tools/tail_push_stats.py, RMAT-26):
-// 179K tail pushers, 40.7M pushed edges, 42.5M code slots, 6.9M distinct targets.
-template <int W>
-__global__ __launch_bounds__(kBlock) void k_push_tail_after(
-    const int32_t* fl, int64_t nf, int32_t H, const int64_t* rowptr, const int32_t* col,
-    const uint64_t* R, const uint32_t* code, int32_t code_from, uint64_t* O, uint32_t* fbm,
-    uint32_t* anyvis, Ctr* ctr, uint32_t* slabF) {
-  __shared__ uint32_t cnt[64 * W];
-  __shared__ unsigned long long scratch[kWaves];
-  __shared__ uint32_t scratch32[kWaves];
-  for (int i = threadIdx.x; i < 64 * W; i += kBlock) cnt[i] = 0;
-  __syncthreads();
-  unsigned long long ef = 0, ev = 0;
-  uint32_t nfc = 0;
-  const int lane = lane_id();
-  const int64_t grp = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-  const int64_t ngrp = ((int64_t)gridDim.x * kBlock) >> 6;
-  for (int64_t i = grp; i < nf; i += ngrp) {
-    const int32_t u = fl[i];
-    if (u < H) continue;
-    const uint32_t c = (code && u >= code_from) ? code[u] : kDenseCode;
-    if (c == 0) continue;
-    const int64_t b = rowptr[u], e = rowptr[u + 1];
-    for (int64_t k = b + lane; k < e; k += 64) {
-      const int32_t v = col[k];
-      // (every target has its output row: the tiles and the big vertices' finalize write one
-      // for the vertices done before this level too, holding every alive group)
-      bool added = false;
-      if (c != kDenseCode) {
-        for (int s = 0; s < kCodeSlots; ++s) {
-          const int g = code_g(c, s);
-          if (g < 0) continue;
-          unsigned long long* p = (unsigned long long*)&O[(int64_t)v * W + (g >> 6)];
-          const unsigned long long bit = 1ull << (g & 63);
-          if (*p & bit) continue;  // (set by the pull or an earlier push: bits only get set)
-          if (!(atomicOr(p, bit) & bit)) {
-            atomicAdd(&cnt[g], 1u);
-            added = true;
-          }
-        }
-      } else {
-        for (int j = 0; j < W; ++j) {
-          const uint64_t w = R[(int64_t)u * W + j];
-          if (!w) continue;
-          uint64_t nb = w & ~(uint64_t)atomicOr((unsigned long long*)&O[(int64_t)v * W + j],
-                                                (unsigned long long)w);
-          added |= nb != 0;
-          while (nb) {
-            atomicAdd(&cnt[j * 64 + __ffsll((unsigned long long)nb) - 1], 1u);
-            nb &= nb - 1;
-          }
-        }
-      }
-      if (added) {  // (plain loads first: most targets got new bits from the pull already)
-        const uint32_t m = 1u << (v & 31);
-        const bool in_f = (fbm[v >> 5] & m) != 0, seen = (anyvis[v >> 5] & m) != 0;
-        if (!in_f || !seen) {
-          const unsigned long long dv = (unsigned long long)(rowptr[v + 1] - rowptr[v]);
-          if (!in_f && !(atomicOr(&fbm[v >> 5], m) & m)) {
-            ++nfc;
-            ef += dv;
-          }
-          if (!seen && !(atomicOr(&anyvis[v >> 5], m) & m)) ev += dv;
-        }
-      }
-    }
-  }
-  block_sum_add32(nfc, &ctr->fl2.v, scratch32);
-  block_sum_add(ef, &ctr->ef2.v, scratch);
-  block_sum_add(ev, &ctr->ev2.v, scratch);
-  __syncthreads();
-  uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-  for (int i = threadIdx.x; i < 64 * W; i += kBlock) row[i] = cnt[i];
-}
 
 // ---------------------------------------------------------------------------------------------
 // bottom-up, narrow vertices: G lanes per vertex, early exit when every alive group is covered.
 // Each step takes C = 8 neighbours: the group's G lanes load and filter them cooperatively
 // (8/G column ids + 8/G bitmap probes per lane instead of 8 + 8), then every lane pulls its
 // slot of each surviving neighbour's row (ids broadcast inside the group by shuffles).
+// A variant is one config type (below, named after the plan's kinds) with the members:
 // BT = block size; HUBW > 0: probes of the HUBW*32 lowest ids (hubs) read an LDS snapshot of
 // the visited bitmap (see k_bu_chunks; big blocks amortise the copy).
 // ---------------------------------------------------------------------------------------------
@@ -364,14 +33,55 @@ __global__ __launch_bounds__(kBlock) void k_push_tail_after(
 // levels are mostly covered by the first neighbour or two (sorted rows: hubs first).
 // FBM: the new frontier goes into the bitmap fbm (passed as fl2) and its size into ctr->fl2, no
 // frontier list (the prefix level at few words, whose next level pulls: see level_bu).
-template <int W, bool COUNT, int BT, int HUBW, bool FUSE, bool FILT = true, bool PFX = false,
-          int CS = 8, int C1 = 0, int MINW = 4, bool FBM = false>
-__global__ __launch_bounds__(BT, MINW) void k_bu_narrow(
+// MINW = waves per SIMD the launch bounds ask for.
+struct NarrowBase {  // the plain filtered 256-thread pull; the variants override what differs
+  static constexpr int BT = kBlock, HUBW = 0, CS = 8, C1 = 0, MINW = 4;
+  static constexpr bool FILT = true, PFX = false, FBM = false;
+};
+// the prefix level (PullKind::Prefix). 4-neighbour steps when fused: 122 VGPRs, no spills
+// (8-neighbour steps spilled at the 128-VGPR bound): RMAT-26 5.17 -> 4.96 ms (the full pulls of
+// level 3 keep 8: 5.8 vs 6.8 ms); FBM: frontier bitmap in place of the list (PullPlan::fbm_out)
+template <int W, bool FUSE_>
+struct NarrowPrefix : NarrowBase {
+  static constexpr bool FUSE = FUSE_, PFX = true, FBM = FUSE_;
+  static constexpr int BT = pfx_block(W), HUBW = kHubW, CS = FUSE_ ? 4 : 8,
+                       MINW = FUSE_ ? pfx_minw(W) : 4;
+};
+template <bool FUSE_>
+struct NarrowHub : NarrowBase {  // PullKind::Hub, the small LDS hub bitmap
+  static constexpr bool FUSE = FUSE_;
+  static constexpr int BT = 1024, HUBW = kHubW;
+};
+template <bool FUSE_>
+struct NarrowHubBig : NarrowBase {  // PullKind::Hub with PullPlan::hub_big
+  static constexpr bool FUSE = FUSE_;
+  static constexpr int BT = 1024, HUBW = kHubBig;
+};
+template <bool FUSE_>
+struct NarrowFiltered : NarrowBase {  // PullKind::Narrow with PullPlan::filter
+  static constexpr bool FUSE = FUSE_;
+};
+template <bool FUSE_>
+struct NarrowPlain : NarrowBase {  // PullKind::Narrow, no probes
+  static constexpr bool FUSE = FUSE_, FILT = false;
+};
+// 8-row steps after a 1-row first step: PullPlan::short1, the lean pass's overflow list and the
+// device-driven batches (all fused: an edge-counting run takes none of them)
+template <bool FUSE_>
+struct NarrowShort1 : NarrowBase {
+  static constexpr bool FUSE = FUSE_, FILT = false;
+  static constexpr int C1 = 1;
+};
+
+template <int W, class Cfg>
+__global__ __launch_bounds__(Cfg::BT, Cfg::MINW) void k_bu_narrow(
     const int32_t* act, int64_t nact, const int64_t* rowptr, const int32_t* col,
     const uint64_t* R, uint64_t* Wb, const uint64_t* alive, const uint64_t* gmask, uint32_t* done,
     int32_t* act2, int32_t* fl2, Ctr* ctr, uint32_t* anyvis, int32_t filter_from, int32_t* actw2,
     int next_wide, uint32_t* slabF, uint64_t* pacc, const int32_t* stamp, int32_t epoch,
     const int32_t* plen, const uint32_t* nact_dev, const uint32_t* snap, BuGate gate) {
+  constexpr int BT = Cfg::BT, HUBW = Cfg::HUBW, CS = Cfg::CS, C1 = Cfg::C1;
+  constexpr bool FUSE = Cfg::FUSE, FILT = Cfg::FILT, PFX = Cfg::PFX, FBM = Cfg::FBM;
   static_assert(!PFX || HUBW > 0, "the prefix pull relies on the LDS hub bitmap");
   if (!bu_gate_open(gate)) return;  // closed level of a device-driven batch (uniform)
   // snap (first pull level of a batch that did not clear its visited buffer, see start_batch):
@@ -379,7 +89,6 @@ __global__ __launch_bounds__(BT, MINW) void k_bu_narrow(
   // this level may still have a stale row) and an own row it does not mark is all zero.
   const uint32_t* pvis = snap ? snap : anyvis;
   if (nact_dev) nact = (int64_t)*nact_dev;  // (list length known only on the device)
-  static_assert(!(FUSE && COUNT), "the edge-counting pass uses k_count_frontier");
   using L = Lay<W>;
   constexpr int VW = L::VW, G = L::G, VPW = L::VPW;
   // done / any-visited bits: one atomic per word of the wave (wave_set_bits) where a wave
@@ -392,29 +101,27 @@ __global__ __launch_bounds__(BT, MINW) void k_bu_narrow(
   __shared__ LdsQueue qa, qf, qw;
   __shared__ unsigned long long scratch[NWV];
   __shared__ uint32_t hub[HUBW > 0 ? HUBW : 1];
-  // counter rows of CR words per 64 groups, bank-skewed (see BitCounter::spill_strided) except
-  // on the prefix level: its sparse spills ran level 2 ~0.2 ms slower skewed (4 runs each)
-  constexpr int CR = PFX ? 64 : 65;
-  __shared__ uint32_t cnt[FUSE ? CR * W : 1];
+  const int lane = lane_id(), slot = lane % G, sub = lane / G;
+  const int wv = threadIdx.x >> 6;
+  // counter rows bank-skewed (65, see spill_strided) except on the prefix level: its sparse
+  // spills ran level 2 ~0.2 ms slower skewed (4 runs each); 5 slices there, 6 elsewhere
+  using Counts = GroupCounts<W, PFX ? 5 : 6, PFX ? 64 : 65, false>;
+  __shared__ uint32_t cnt[FUSE ? Counts::kLdsWords : 1];
+  Counts gc(cnt, slot);
   if constexpr (HUBW > 0)
     for (int i = threadIdx.x; i < HUBW; i += BT) hub[i] = pvis[i];
-  if constexpr (FUSE)
-    for (int i = threadIdx.x; i < CR * W; i += BT) cnt[i] = 0;
+  if constexpr (FUSE) gc.zero(BT);
   q_init(qa);
   q_init(qf);
   q_init(qw);
   __syncthreads();
-  const int lane = lane_id(), slot = lane % G, sub = lane / G;
-  const int wv = threadIdx.x >> 6;
+  // (written out, not alive_mask: the helper costs the fused hub variant at 4 words 2 spills)
   V<VW> am;
 #pragma unroll
   for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
   unsigned long long eu = 0, ef = 0, ev = 0;
   uint32_t nfc = 0;  // FBM: new frontier vertices
   __shared__ uint32_t scratch32[FBM ? NWV : 1];
-  BitCounter<VW, PFX ? 5 : 6> bc;
-  int nadd = 0;
-  if constexpr (FUSE) bc.zero();
   // Software pipeline over the grid-stride tiles: the active-list entry is loaded two tiles
   // ahead and the vertex's visited row and row offsets one tile ahead, so a tile starts with
   // its column loads instead of two dependent round trips (list entry -> row / offsets).
@@ -428,7 +135,7 @@ __global__ __launch_bounds__(BT, MINW) void k_bu_narrow(
   if (tb + stride + lofs < nact) v2 = act[tb + stride + lofs];
   uint32_t p1 = 0;  // PFX: prefix length of v1's row (ids < H)
   if (tb + lofs < nact) {
-    r1 = (snap && !any_visited(snap, v1)) ? vzero<VW>() : ldv<VW>(R + (int64_t)v1 * W + slot * VW);
+    r1 = own_row<VW>(R, snap, v1, (int64_t)v1 * W + slot * VW);
     b1 = rowptr[v1];
     d1 = (uint32_t)(rowptr[v1 + 1] - b1);
     if constexpr (PFX) p1 = (uint32_t)plen[v1];
@@ -461,20 +168,19 @@ __global__ __launch_bounds__(BT, MINW) void k_bu_narrow(
     // prefetch: row / offsets of the next tile, list entry of the one after
     v1 = v2;
     if (idx + stride < nact) {
-      r1 = (snap && !any_visited(snap, v1)) ? vzero<VW>() : ldv<VW>(R + (int64_t)v1 * W + slot * VW);
+      r1 = own_row<VW>(R, snap, v1, (int64_t)v1 * W + slot * VW);
       b1 = rowptr[v1];
       d1 = (uint32_t)(rowptr[v1 + 1] - b1);
       if constexpr (PFX) p1 = (uint32_t)plen[v1];
     }
     if (idx + 2 * stride < nact) v2 = act[idx + 2 * stride];
     V<VW> unv = vzero<VW>(), acc = vzero<VW>();
-    bool lane_open = false, rnz = false;
+    bool lane_open = false;
     if (valid) {
 #pragma unroll
       for (int j = 0; j < VW; ++j) {
         unv.w[j] = ~r.w[j] & am.w[j];
         lane_open |= unv.w[j] != 0;
-        rnz |= r.w[j] != 0;
       }
     }
     if constexpr (PFX) {  // bits pushed from the tail frontier (k_push_tail)
@@ -575,40 +281,12 @@ __global__ __launch_bounds__(BT, MINW) void k_bu_narrow(
 
       }
     }
-    V<VW> nw;
-    bool anynew = false, notfull = false;
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      nw.w[j] = acc.w[j] & unv.w[j];
-      anynew |= nw.w[j] != 0;
-      notfull |= (unv.w[j] & ~nw.w[j]) != 0;
-    }
-    if (valid) {  // also when nothing is open: Wb may hold the previous batch's rows
-      V<VW> nv;
-#pragma unroll
-      for (int j = 0; j < VW; ++j) nv.w[j] = r.w[j] | nw.w[j];
-      stv<VW>(Wb + (int64_t)v * W + slot * VW, nv);
-    }
-    if constexpr (FUSE) {  // nw is zero for invalid lanes
-      bc.add(nw);
-      if (++nadd == (1 << BitCounter<VW, PFX ? 5 : 6>::D) - 1) {
-        bc.template spill_strided<CR>(cnt, slot);
-        nadd = 0;
-      }
-    }
-    const uint64_t bn = __ballot(anynew), bf = __ballot(notfull);
-    const bool g_new = (bn >> (sub * G)) & L::GBITS;
-    const bool g_nf = (bf >> (sub * G)) & L::GBITS;
-    const bool leader = valid && slot == 0;
-    wave_set_bits<kCombine>(done, v, leader && !g_nf);
-    const bool keep = leader && g_nf, app = leader && g_new;
-    if (keep) eu += deg;
-    if (app) ef += deg;
-    {
-      const bool g_first = g_new && !((__ballot(rnz) >> (sub * G)) & L::GBITS);
-      wave_set_bits<kCombine>(anyvis, v, leader && g_first);
-      if (leader && g_first) ev += deg;
-    }
+    const NewBits<VW> nb = gained(r, acc, unv);  // (unv is zero on lanes without a vertex)
+    // also when nothing is open: Wb may hold the previous batch's rows
+    if (valid) stv<VW>(Wb + (int64_t)v * W + slot * VW, nb.nv);
+    if constexpr (FUSE) gc.add(nb.nw);
+    const auto [keep, app, g_nf] =
+        settle_vertex<W, kCombine>(valid, v, deg, nb, done, anyvis, eu, ef, ev);
     // third stage: the next tile's first-step ids (its offsets arrived during this tile)
     first_ids(idx + stride < nact, u1);
     q_push(qa, keep && (int)deg <= next_wide, v);
@@ -633,12 +311,7 @@ __global__ __launch_bounds__(BT, MINW) void k_bu_narrow(
   block_sum_add(eu, &ctr->eu2.v, scratch);
   block_sum_add(ef, &ctr->ef2.v, scratch);
   block_sum_add(ev, &ctr->ev2.v, scratch);
-  if constexpr (FUSE) {
-    bc.template spill_strided<CR>(cnt, slot);
-    __syncthreads();
-    uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-    for (int i = threadIdx.x; i < 64 * W; i += BT) row[i] = cnt[CR == 65 ? i + (i >> 6) : i];
-  }
+  if constexpr (FUSE) gc.store(slabF, BT);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -666,23 +339,20 @@ __global__ __launch_bounds__(kBlock, W >= 16 ? 8 : 6) void k_bu_first(
   // done / any-visited bits: one atomic per word of the wave (wave_set_bits) where a wave
   // holds many vertices or many first visits (W = 16 levels 3-4 measured ~0.4 ms slower each)
   constexpr bool kCombine = G <= 4;
-  constexpr int CR = 65;  // bank-skewed counter rows (see BitCounter::spill_strided)
+  const int lane = lane_id(), slot = lane % G, sub = lane / G;
+  const int wv = threadIdx.x >> 6;
+  // bank-skewed counter rows (see spill_strided), 32-bit halves (see spill_strided32)
+  using Counts = GroupCounts<W, 6, 65, true>;
   __shared__ LdsQueue qo, qf;
   __shared__ unsigned long long scratch[kWaves];
-  __shared__ uint32_t cnt[CR * W];
-  for (int i = threadIdx.x; i < CR * W; i += kBlock) cnt[i] = 0;
+  __shared__ uint32_t cnt[Counts::kLdsWords];
+  Counts gc(cnt, slot);
+  gc.zero(kBlock);
   q_init(qo);
   q_init(qf);
   __syncthreads();
-  const int lane = lane_id(), slot = lane % G, sub = lane / G;
-  const int wv = threadIdx.x >> 6;
-  V<VW> am;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  const V<VW> am = alive_mask<VW>(alive, gmask, slot);
   unsigned long long ef = 0, ev = 0;
-  BitCounter<VW> bc;
-  bc.zero();
-  int nadd = 0;
   for (int64_t tb = (int64_t)blockIdx.x * TILE; tb < nact; tb += (int64_t)gridDim.x * TILE) {
     const int64_t idx = tb + wv * VPW + sub;
     const bool valid = idx < nact;
@@ -719,11 +389,8 @@ __global__ __launch_bounds__(kBlock, W >= 16 ? 8 : 6) void k_bu_first(
       for (int j = 0; j < VW; ++j) nv.w[j] = r.w[j] | nw.w[j];
       stv<VW>(Wb + (int64_t)v * W + slot * VW, nv);
     }
-    bc.add(nw);
-    if (++nadd == (1 << BitCounter<VW>::D) - 1) {
-      bc.template spill_strided32<CR>(cnt, slot);
-      nadd = 0;
-    }
+    gc.add(nw);
+    // (own epilogue: the done bit follows the first-row coverage `fin`, not the new bits)
     bool anynew = false;
 #pragma unroll
     for (int j = 0; j < VW; ++j) anynew |= nw.w[j] != 0;
@@ -743,10 +410,7 @@ __global__ __launch_bounds__(kBlock, W >= 16 ? 8 : 6) void k_bu_first(
   q_flush(qf, fl2, &ctr->fl2.v, 0, true);
   block_sum_add(ef, &ctr->ef2.v, scratch);
   block_sum_add(ev, &ctr->ev2.v, scratch);
-  bc.template spill_strided32<CR>(cnt, slot);
-  __syncthreads();
-  uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-  for (int i = threadIdx.x; i < 64 * W; i += kBlock) row[i] = cnt[i + (i >> 6)];
+  gc.store(slabF, kBlock);
 }
 
 // bottom-up, wide vertices, phase 1: one wave per edge chunk (<= kChunk edges), processed in
@@ -782,7 +446,7 @@ __device__ __forceinline__ void chunk_pull(int32_t v, int64_t beg, int64_t lim, 
   constexpr int PB = VW == 2 ? 4 : 8;  // rows in flight per lane group in phase B
   const int lane = lane_id(), slot = lane % G, sub = lane / G;
   const int64_t vo = (int64_t)v * W + slot * VW;
-  const V<VW> r = (snap && !any_visited(snap, v)) ? vzero<VW>() : ldv<VW>(R + vo);  // see k_bu_narrow
+  const V<VW> r = own_row<VW>(R, snap, v, vo);  // see k_bu_narrow
   // g = bits the vertex's other chunks have published so far. Chunks of one hub run
   // concurrently, so each tile publishes its partial OR with a RETURNING atomicOr that also
   // hands back the current union from the memory side (atomics bypass the non-coherent per-XCD
@@ -883,48 +547,18 @@ __device__ __forceinline__ void chunk_pull(int32_t v, int64_t beg, int64_t lim, 
     __builtin_amdgcn_wave_barrier();
     // ---- phase B: rows of the surviving neighbours, PB per lane group per step
     for (int b = 0; b < cnt; b += PB * S) {
-      int32_t uu[PB];
-#pragma unroll
-      for (int q = 0; q < PB; ++q) {
-        const int k = b + q * S + sub;
-        uu[q] = k < cnt ? lst[k] : -1;
-      }
-      {
-        // loads first, ORs after: the compiler then keeps all PB loads in flight
-        V<VW> x[PB];
-#pragma unroll
-        for (int q = 0; q < PB; ++q) {
-          x[q] = vzero<VW>();
-          if (uu[q] >= 0) x[q] = ldv<VW>(R + (int64_t)uu[q] * W + slot * VW);
-        }
-#pragma unroll
-        for (int q = 0; q < PB; ++q)
-#pragma unroll
-          for (int j = 0; j < VW; ++j) a.w[j] |= x[q].w[j];
-      }
+      gather_rows<W, PB, false>(lst, cnt, b, R, a);
       if (each) {
-#pragma unroll
-        for (int off = G; off < 64; off <<= 1)
-#pragma unroll
-          for (int j = 0; j < VW; ++j) a.w[j] |= __shfl_xor(a.w[j], off);
-        bool cov = true;
-#pragma unroll
-        for (int j = 0; j < VW; ++j) cov &= ((a.w[j] | g.w[j]) & unv.w[j]) == unv.w[j];
-        if (!__ballot(!cov)) {
+        or_across_groups<VW, G>(a);
+        if (covers(a, g, unv)) {
           covered = true;
           break;
         }
       }
     }
     if (!each) {  // one cross-group OR and coverage check per tile (see `each`)
-#pragma unroll
-      for (int off = G; off < 64; off <<= 1)
-#pragma unroll
-        for (int j = 0; j < VW; ++j) a.w[j] |= __shfl_xor(a.w[j], off);
-      bool cov = true;
-#pragma unroll
-      for (int j = 0; j < VW; ++j) cov &= ((a.w[j] | g.w[j]) & unv.w[j]) == unv.w[j];
-      if (!__ballot(!cov)) covered = true;
+      or_across_groups<VW, G>(a);
+      if (covers(a, g, unv)) covered = true;
     }
     __builtin_amdgcn_wave_barrier();  // lst is rewritten by the next tile
     // publish this chunk's bits so far and pick up the other chunks' (one round trip)
@@ -974,6 +608,7 @@ __device__ __forceinline__ void chunk_pull_pfx(int32_t v, int64_t beg, int64_t l
   constexpr int Q = T / 64;
   const int lane = lane_id(), slot = lane % G, sub = lane / G;
   const int64_t vo = (int64_t)v * W + slot * VW;
+  // (written out, not own_row: the helper costs this kernel 2 VGPRs)
   const V<VW> r = (snap && !any_visited(snap, v)) ? vzero<VW>() : ldv<VW>(R + vo);
   V<VW> unv, a = vzero<VW>();
   bool lane_open = false;
@@ -1018,35 +653,11 @@ __device__ __forceinline__ void chunk_pull_pfx(int32_t v, int64_t beg, int64_t l
       cnt += __popcll(m);
     }
     __builtin_amdgcn_wave_barrier();
-    for (int b = 0; b < cnt; b += PB * S) {
-      int32_t uu[PB];
-#pragma unroll
-      for (int q = 0; q < PB; ++q) {
-        const int k = b + q * S + sub;
-        const int32_t x = lst[k < cnt ? k : 0];
-        uu[q] = k < cnt ? x : -1;
-      }
-      // (idle lanes load nothing: their address costs the address unit as much as a row)
-      V<VW> x[PB];
-#pragma unroll
-      for (int q = 0; q < PB; ++q) {
-        x[q] = vzero<VW>();
-        if (uu[q] >= 0) x[q] = ldv<VW>(R + (int64_t)uu[q] * W + slot * VW);
-      }
-#pragma unroll
-      for (int q = 0; q < PB; ++q)
-#pragma unroll
-        for (int j = 0; j < VW; ++j) a.w[j] |= x[q].w[j];
-    }
+    // (unconditional LDS reads from a clamped index, as every load of this pull)
+    for (int b = 0; b < cnt; b += PB * S) gather_rows<W, PB, true>(lst, cnt, b, R, a);
     // one cross-group OR and coverage check per tile
-#pragma unroll
-    for (int off = G; off < 64; off <<= 1)
-#pragma unroll
-      for (int j = 0; j < VW; ++j) a.w[j] |= __shfl_xor(a.w[j], off);
-    bool cov = true;
-#pragma unroll
-    for (int j = 0; j < VW; ++j) cov &= (a.w[j] & unv.w[j]) == unv.w[j];
-    if (!__ballot(!cov)) covered = true;
+    or_across_groups<VW, G>(a);
+    if (covers(a, vzero<VW>(), unv)) covered = true;
     __builtin_amdgcn_wave_barrier();  // lst is rewritten by the next tile
   }
   if (sub == 0) {
@@ -1054,143 +665,6 @@ __device__ __forceinline__ void chunk_pull_pfx(int32_t v, int64_t beg, int64_t l
     for (int j = 0; j < VW; ++j) {
       const uint64_t nb = a.w[j] & unv.w[j];
       if (nb) atomicOr((unsigned long long*)&acc[vo + j], nb);
-    }
-  }
-}
-
-// Chunk descriptor: vertex, first column position, edge count (<= kChunk). Built once per level
-// by k_chunk_desc; a wave reads its next descriptor with one scalar load while it pulls the
-// current chunk (vs an owner -> list entry -> row offsets chain of dependent loads per chunk).
-struct ChunkDesc {
-  int32_t v;
-  uint32_t beg_lo, beg_hi;
-  int32_t len;
-};
-
-// first position in the sorted row [b, e) whose id is >= H
-__device__ __forceinline__ int64_t row_lower_bound(const int32_t* col, int64_t b, int64_t e,
-                                                   int32_t H) {
-  while (b < e) {
-    const int64_t mid = (b + e) >> 1;
-    if (col[mid] < H) b = mid + 1;
-    else e = mid;
-  }
-  return b;
-}
-
-// plen[v] = length of v's row prefix with ids < H (rows sorted; a graph property, computed once
-// per graph and bound H, see BitparSolver::prefix_lens)
-static __global__ __launch_bounds__(kBlock) void k_prefix_lens(const int64_t* rowptr, const int32_t* col,
-                                                        int64_t n, int32_t H, int32_t* plen) {
-  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n;
-       v += (int64_t)gridDim.x * kBlock) {
-    const int64_t b = rowptr[v];
-    plen[v] = (int32_t)(row_lower_bound(col, b, rowptr[v + 1], H) - b);
-  }
-}
-
-// first[v] = v's first neighbour (rows sorted: after degree relabelling its biggest hub), -1 for
-// an isolated vertex: the lean first-row pass (k_bu_first) reads it with one coalesced 4-byte load
-// instead of the rowptr -> col chain, whose col[rowptr[v]] touches one 128-byte line per vertex
-static __global__ __launch_bounds__(kBlock) void k_first_nbr(const int64_t* rowptr, const int32_t* col,
-                                                      int64_t n, int32_t* first) {
-  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n;
-       v += (int64_t)gridDim.x * kBlock) {
-    const int64_t b = rowptr[v];
-    first[v] = rowptr[v + 1] > b ? col[b] : -1;
-  }
-}
-
-// chunk counts of the wide vertices' row prefixes (inclusive-scanned into offs by the host)
-static __global__ __launch_bounds__(kBlock) void k_prefix_chunks(const int32_t* wl, int64_t nw,
-                                                          const int32_t* plen, int64_t* cnt) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nw;
-       i += (int64_t)gridDim.x * kBlock)
-    cnt[i] = ((int64_t)plen[wl[i]] + kChunk - 1) / kChunk;
-}
-
-// plen != nullptr: chunks cover only the row prefixes with ids < H (prefix-pull level)
-static __global__ __launch_bounds__(kBlock) void k_chunk_desc(const int32_t* wl, int64_t nw,
-                                                       const int64_t* offs, const int64_t* rowptr,
-                                                       const int32_t* plen, ChunkDesc* desc) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nw;
-       i += (int64_t)gridDim.x * kBlock) {
-    const int32_t v = wl[i];
-    const int64_t b = rowptr[v];
-    const int64_t e = plen ? b + plen[v] : rowptr[v + 1];
-    const int64_t c0 = i ? offs[i - 1] : 0, c1 = offs[i];
-    for (int64_t c = c0; c < c1; ++c) {
-      const int64_t cb = b + (c - c0) * kChunk;
-      desc[c] = ChunkDesc{v, (uint32_t)cb, (uint32_t)((uint64_t)cb >> 32),
-                          (int32_t)min((int64_t)kChunk, e - cb)};
-    }
-  }
-}
-
-// Two-pass chunk scheduling on the early-exit levels (tuning key chunk2): pass 1 pulls only the
-// first chunk of every wide vertex (most are covered by the hubs at the head of their sorted
-// rows), pass 2 only the remaining chunks of the vertices pass 1 left open. In one pass every
-// chunk of a covered vertex still cost its wave an own-row load and a returning atomic before
-// it could skip (RMAT-26 level 3: 313K wide vertices, ~1M+ chunks, 0.5 ms).
-static __global__ __launch_bounds__(kBlock) void k_chunk_first(const int32_t* wl, int64_t nw,
-                                                               const int64_t* rowptr,
-                                                               ChunkDesc* desc, int64_t* cnt) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nw;
-       i += (int64_t)gridDim.x * kBlock) {
-    const int32_t v = wl[i];
-    const int64_t b = rowptr[v], e = rowptr[v + 1];
-    desc[i] = ChunkDesc{v, (uint32_t)b, (uint32_t)((uint64_t)b >> 32),
-                        (int32_t)min((int64_t)kChunk, e - b)};
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) *cnt = nw;
-}
-// chunks left of wide vertex i after pass 1: 0 once acc[v] (the union its chunks published)
-// covers every alive group v misses, else all but the first (G lanes per vertex)
-template <int W>
-__global__ __launch_bounds__(kBlock) void k_chunk_rest_count(
-    const int32_t* wl, int64_t nw, const int64_t* rowptr, const uint64_t* R, const uint64_t* acc,
-    const uint64_t* alive, const uint64_t* gmask, const uint32_t* snap, int64_t* cnt) {
-  using L = Lay<W>;
-  constexpr int VW = L::VW, G = L::G, VPW = L::VPW, TILE = L::TILE;
-  const int lane = lane_id(), slot = lane % G, sub = lane / G, wv = threadIdx.x >> 6;
-  V<VW> am;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
-  for (int64_t tb = (int64_t)blockIdx.x * TILE; tb < nw; tb += (int64_t)gridDim.x * TILE) {
-    const int64_t i = tb + wv * VPW + sub;
-    bool open = false;
-    int32_t v = 0;
-    if (i < nw) {
-      v = wl[i];
-      const int64_t vo = (int64_t)v * W + slot * VW;
-      const V<VW> r = (snap && !any_visited(snap, v)) ? vzero<VW>() : ldv<VW>(R + vo);
-      const V<VW> a = ldv<VW>(acc + vo);
-#pragma unroll
-      for (int j = 0; j < VW; ++j) open |= (~r.w[j] & am.w[j] & ~a.w[j]) != 0;
-    }
-    const bool g_open = (__ballot(open) >> (sub * G)) & L::GBITS;
-    if (i < nw && slot == 0) {
-      const int64_t d = rowptr[v + 1] - rowptr[v];
-      const int64_t nc = (d + kChunk - 1) / kChunk;
-      cnt[i] = g_open && nc > 1 ? nc - 1 : 0;
-    }
-  }
-}
-// descriptors of the pass-2 chunks (offs = inclusive prefix of k_chunk_rest_count)
-static __global__ __launch_bounds__(kBlock) void k_chunk_rest_desc(const int32_t* wl, int64_t nw,
-                                                                   const int64_t* offs,
-                                                                   const int64_t* rowptr,
-                                                                   ChunkDesc* desc) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nw;
-       i += (int64_t)gridDim.x * kBlock) {
-    const int64_t c0 = i ? offs[i - 1] : 0, c1 = offs[i];
-    if (c0 == c1) continue;
-    const int32_t v = wl[i];
-    const int64_t b = rowptr[v], e = rowptr[v + 1];
-    for (int64_t c = c0; c < c1; ++c) {
-      const int64_t cb = b + (1 + c - c0) * kChunk;
-      desc[c] = ChunkDesc{v, (uint32_t)cb, (uint32_t)((uint64_t)cb >> 32),
-                          (int32_t)min((int64_t)kChunk, e - cb)};
     }
   }
 }
@@ -1218,9 +692,7 @@ __global__ __launch_bounds__(BT, (BT >= 1024 && HUBW <= 16384) ? 8 : 4) void k_b
   const int64_t nchunks = uni64(*nchunks_p);  // inclusive chunk prefix of the last wide vertex
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  V<VW> am;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  const V<VW> am = alive_mask<VW>(alive, gmask, slot);
   // Chunk order. Without early exit (coop = 0: the first bottom-up level, where hardly any row
   // is covered) chunks are dealt round robin over the waves, which balances the hubs' expensive
   // chunks. With early exit a wave takes a contiguous run, so a vertex's later chunks usually
@@ -1244,7 +716,7 @@ __global__ __launch_bounds__(BT, (BT >= 1024 && HUBW <= 16384) ? 8 : 4) void k_b
 }
 
 // bottom-up, wide vertices, phase 2: G lanes per vertex fold acc[v] into the visited words.
-template <int W, bool COUNT, bool FUSE, bool FLB = false>
+template <int W, bool FUSE, bool FLB = false>
 __global__ __launch_bounds__(kBlock) void k_bu_wide_finalize(
     const int32_t* wl, int64_t nw, const int64_t* rowptr, const uint64_t* R, uint64_t* Wb,
     uint64_t* acc, const uint64_t* alive, const uint64_t* gmask, uint32_t* done, int32_t* actw2,
@@ -1262,24 +734,19 @@ __global__ __launch_bounds__(kBlock) void k_bu_wide_finalize(
   constexpr bool kCombine = G <= 4;
   __shared__ LdsQueue qa, qf, qn;
   __shared__ unsigned long long scratch[kWaves];
-  // bank-skewed counter rows (see BitCounter::spill_strided): wide vertices gain many groups
-  // at once, so every spill touches most counters
-  constexpr int CR = 65;
-  __shared__ uint32_t cnt[FUSE ? CR * W : 1];
-  if constexpr (FUSE)
-    for (int i = threadIdx.x; i < CR * W; i += kBlock) cnt[i] = 0;
+  const int lane = lane_id(), slot = lane % G, sub = lane / G;
+  const int wv = threadIdx.x >> 6;
+  // bank-skewed counter rows (see spill_strided): wide vertices gain many groups at once, so
+  // every spill touches most counters
+  using Counts = GroupCounts<W, 6, 65, false>;
+  __shared__ uint32_t cnt[FUSE ? Counts::kLdsWords : 1];
+  Counts gc(cnt, slot);
+  if constexpr (FUSE) gc.zero(kBlock);
   q_init(qa);
   q_init(qf);
   q_init(qn);
   __syncthreads();
-  BitCounter<VW> bc;
-  int nadd = 0;
-  if constexpr (FUSE) bc.zero();
-  const int lane = lane_id(), slot = lane % G, sub = lane / G;
-  const int wv = threadIdx.x >> 6;
-  V<VW> am;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  const V<VW> am = alive_mask<VW>(alive, gmask, slot);
   unsigned long long eu = 0, ef = 0, ev = 0;
   uint32_t nfc = 0;
   __shared__ uint32_t scratch32[kWaves];
@@ -1287,8 +754,7 @@ __global__ __launch_bounds__(kBlock) void k_bu_wide_finalize(
     const int64_t idx = tb + wv * VPW + sub;
     bool valid = idx < nw;
     int32_t v = 0;
-    V<VW> nwb = vzero<VW>();
-    bool anynew = false, notfull = false, rnz = false;
+    NewBits<VW> nb{vzero<VW>(), vzero<VW>(), false, false, false};
     uint32_t deg = 0;
     if (valid) {
       v = wl[idx];
@@ -1303,42 +769,16 @@ __global__ __launch_bounds__(kBlock) void k_bu_wide_finalize(
     }
     if (valid) {
       const int64_t vo = (int64_t)v * W + slot * VW;
-      const V<VW> r = (snap && !any_visited(snap, v)) ? vzero<VW>() : ldv<VW>(R + vo);
+      const V<VW> r = own_row<VW>(R, snap, v, vo);
       const V<VW> a = ldv<VW>(acc + vo);
-      V<VW> nv;
-#pragma unroll
-      for (int j = 0; j < VW; ++j) {
-        const uint64_t unv = ~r.w[j] & am.w[j];
-        nwb.w[j] = a.w[j] & unv;
-        nv.w[j] = r.w[j] | nwb.w[j];
-        anynew |= nwb.w[j] != 0;
-        notfull |= (unv & ~nwb.w[j]) != 0;
-        rnz |= r.w[j] != 0;
-      }
+      nb = new_bits(r, a, am);
       stv<VW>(acc + vo, vzero<VW>());
-      stv<VW>(Wb + vo, nv);
+      stv<VW>(Wb + vo, nb.nv);
       deg = (uint32_t)(rowptr[v + 1] - rowptr[v]);
     }
-    if constexpr (FUSE) {  // nwb is zero for invalid lanes
-      bc.add(nwb);
-      if (++nadd == (1 << BitCounter<VW>::D) - 1) {
-        bc.template spill_strided<CR>(cnt, slot);
-        nadd = 0;
-      }
-    }
-    const uint64_t bn = __ballot(anynew), bf = __ballot(notfull);
-    const bool g_new = (bn >> (sub * G)) & L::GBITS;
-    const bool g_nf = (bf >> (sub * G)) & L::GBITS;
-    const bool leader = valid && slot == 0;
-    wave_set_bits<kCombine>(done, v, leader && !g_nf);
-    const bool keep = leader && g_nf, app = leader && g_new;
-    if (keep && (!fbm || FLB)) eu += deg;
-    if (app) ef += deg;
-    {
-      const bool g_first = g_new && !((__ballot(rnz) >> (sub * G)) & L::GBITS);
-      wave_set_bits<kCombine>(anyvis, v, leader && g_first);
-      if (leader && g_first) ev += deg;
-    }
+    if constexpr (FUSE) gc.add(nb.nw);  // (zero for invalid lanes)
+    const auto [keep, app, g_nf] =
+        settle_vertex<W, kCombine>(valid, v, deg, nb, done, anyvis, eu, ef, ev, !fbm || FLB);
     if (fbm) {  // (uniform)
       wave_set_bits<kCombine>(fbm, v, app);
       nfc += app ? 1u : 0u;
@@ -1357,27 +797,7 @@ __global__ __launch_bounds__(kBlock) void k_bu_wide_finalize(
   block_sum_add(eu, &ctr->eu2.v, scratch);
   block_sum_add(ef, &ctr->ef2.v, scratch);
   block_sum_add(ev, &ctr->ev2.v, scratch);
-  if constexpr (FUSE) {
-    bc.template spill_strided<CR>(cnt, slot);
-    __syncthreads();
-    uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-    for (int i = threadIdx.x; i < 64 * W; i += kBlock) row[i] = cnt[i + (i >> 6)];
-  }
-}
-
-// counter slot 0 and alive mask 0 of a device-driven pull batch (bu_batch): the host's view
-// after the level before the batch
-static __global__ void k_bu_seed(Ctr* c0, uint32_t nf, unsigned long long ef, uint32_t nact,
-                          uint32_t nactw, unsigned long long eu, const uint64_t* alive,
-                          uint64_t* alive0) {
-  if (threadIdx.x == 0) {
-    c0->fl2.v = nf;
-    c0->ef2.v = ef;
-    c0->act2.v = nact;
-    c0->actw2.v = nactw;
-    c0->eu2.v = eu;
-  }
-  if (threadIdx.x < 16) alive0[threadIdx.x] = alive[threadIdx.x];
+  if constexpr (FUSE) gc.store(slabF, kBlock);
 }
 
 }  // namespace bp

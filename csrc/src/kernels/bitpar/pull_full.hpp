@@ -102,12 +102,17 @@ __global__ __launch_bounds__(kBlock, W <= 2 ? 5 : 4) void k_bu_full(
   __shared__ int32_t qmem[kWaves][QA + QF + QW];
   __shared__ unsigned long long scratch[kWaves];
   __shared__ uint32_t wbase[kWaves + 1];
-  constexpr int CR = 65;  // bank-skewed counter rows (BitCounter::spill_strided)
-  __shared__ uint32_t cnt[CR * W];
-  for (int i = threadIdx.x; i < CR * W; i += kBlock) cnt[i] = 0;
-  __syncthreads();
   const int lane = lane_id(), slot = lane % G, sub = lane / G;
   const int wv = threadIdx.x >> 6;
+  // Carry-save group counters: 7 slices (a spill every 127 tiles) at 16 words, spilled on
+  // 32-bit halves (~12 VALU per set counter bit instead of ~28: level 3 spills find most
+  // counter bits set, ~50 VALU per tile with 6 slices and 64-bit spills); 5 slices for few
+  // words (one spill every 31 tiles, the 96-VGPR bound); bank-skewed rows (spill_strided)
+  using Counts = GroupCounts<W, W <= 4 ? 5 : (W >= 16 ? 7 : 6), 65, true>;
+  __shared__ uint32_t cnt[Counts::kLdsWords];
+  Counts gc(cnt, slot);
+  gc.zero(kBlock);
+  __syncthreads();
   int32_t* qa = qmem[wv];
   int32_t* qf = qa + QA;
   int32_t* qw = qf + QF;
@@ -116,17 +121,8 @@ __global__ __launch_bounds__(kBlock, W <= 2 ? 5 : 4) void k_bu_full(
   uint64_t* rO = Wb;
   const int voff = slot * VW * 8;
   const int32_t zrow = (int32_t)n;  // the all-zero row (n <= INT32_MAX - 2, see the solver)
-  V<VW> am;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  const V<VW> am = alive_mask<VW>(alive, gmask, slot);
   unsigned long long eu = 0, ef = 0, ev = 0;
-  // Carry-save group counters: 7 slices (a spill every 127 tiles) at 16 words, spilled on
-  // 32-bit halves (~12 VALU per set counter bit instead of ~28: level 3 spills find most
-  // counter bits set, ~50 VALU per tile with 6 slices and 64-bit spills); 5 slices for few
-  // words (one spill every 31 tiles, the 96-VGPR bound)
-  BitCounter<VW, W <= 4 ? 5 : (W >= 16 ? 7 : 6)> bc;
-  bc.zero();
-  int nadd = 0;
   // software pipeline (as k_bu_narrow): list entry two tiles ahead, own row / offsets one tile
   // ahead, the first step's column ids one tile ahead (loaded at the end of the previous tile)
   const int64_t stride = (int64_t)gridDim.x * TILE, lofs = wv * VPW + sub;
@@ -328,40 +324,24 @@ __global__ __launch_bounds__(kBlock, W <= 2 ? 5 : 4) void k_bu_full(
       if (v1 < 0) e1 = b1;
       first_ids(b1, e1, u1);
     }
-    V<VW> nwv;
-    bool anynew = false, notfull = false;
+    // (written out, not gained(): that cost k_bu_full<1, 4, 1> 8 VGPRs)
+    NewBits<VW> nb;
+    nb.anynew = nb.notfull = false;
+    nb.rnz = rnz;
 #pragma unroll
     for (int j = 0; j < VW; ++j) {
-      nwv.w[j] = acc.w[j] & unv.w[j];
-      anynew |= nwv.w[j] != 0;
-      notfull |= (unv.w[j] & ~nwv.w[j]) != 0;
+      nb.nw.w[j] = acc.w[j] & unv.w[j];
+      nb.anynew |= nb.nw.w[j] != 0;
+      nb.notfull |= (unv.w[j] & ~nb.nw.w[j]) != 0;
+      nb.nv.w[j] = r.w[j] | nb.nw.w[j];
     }
-    const uint64_t bn = __ballot(anynew), bf = __ballot(notfull);
-    const bool g_new = (bn >> (sub * G)) & L::GBITS;
-    const bool g_nf = (bf >> (sub * G)) & L::GBITS;
-    {  // also when nothing is open: Wb may hold the previous batch's rows
-      // (skip: a vertex done now is never read again, see above; a store under a branch costs
-      // no wait, and no idle lane hammers the scratch row's one cache line)
-      V<VW> nv;
-#pragma unroll
-      for (int j = 0; j < VW; ++j) nv.w[j] = r.w[j] | nwv.w[j];
-      if (valid && (g_nf || !skip)) st_row<W, VW>(rO, v, voff, nv);
-    }
-    bc.add(nwv);  // (zero for invalid lanes)
-    if (++nadd == (1 << decltype(bc)::D) - 1) {
-      bc.template spill_strided32<CR>(cnt, slot);
-      nadd = 0;
-    }
-    const bool leader = valid && slot == 0;
-    wave_set_bits<kCombine>(done, v, leader && !g_nf);
-    const bool keep = leader && g_nf, app = leader && g_new;
-    if (keep) eu += deg;
-    if (app) ef += deg;
-    {
-      const bool g_first = g_new && !((__ballot(rnz) >> (sub * G)) & L::GBITS);
-      wave_set_bits<kCombine>(anyvis, v, leader && g_first);
-      if (leader && g_first) ev += deg;
-    }
+    gc.add(nb.nw);
+    const auto [keep, app, g_nf] =
+        settle_vertex<W, kCombine>(valid, v, deg, nb, done, anyvis, eu, ef, ev);
+    // the row also when nothing is open: Wb may hold the previous batch's rows
+    // (skip: a vertex done now is never read again, see above; a store under a branch costs
+    // no wait, and no idle lane hammers the scratch row's one cache line)
+    if (valid && (g_nf || !skip)) st_row<W, VW>(rO, v, voff, nb.nv);
     // third stage: the done probe of the next tile's first-step ids (loaded during this tile)
     probe_words(u1, pd1);
     wq_push(qa, na, keep && (int)deg <= next_wide, v);
@@ -379,10 +359,7 @@ __global__ __launch_bounds__(kBlock, W <= 2 ? 5 : 4) void k_bu_full(
   block_sum_add(eu, &ctr->eu2.v, scratch);
   block_sum_add(ef, &ctr->ef2.v, scratch);
   block_sum_add(ev, &ctr->ev2.v, scratch);
-  bc.template spill_strided32<CR>(cnt, slot);
-  __syncthreads();
-  uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-  for (int i = threadIdx.x; i < 64 * W; i += kBlock) row[i] = cnt[i + (i >> 6)];
+  gc.store(slabF, kBlock);
 }
 
 // A push level after a pull level that skipped the rows of its finishing vertices (dskip) reads
@@ -398,9 +375,7 @@ __global__ __launch_bounds__(kBlock) void k_fix_done_rows(const int32_t* fl, con
   constexpr int VW = L::VW, G = L::G, VPW = L::VPW, TILE = L::TILE;
   if (nf_dev) nf = (int64_t)*nf_dev;
   const int lane = lane_id(), slot = lane % G, sub = lane / G, wv = threadIdx.x >> 6;
-  V<VW> am;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) am.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  const V<VW> am = alive_mask<VW>(alive, gmask, slot);
   for (int64_t tb = (int64_t)blockIdx.x * TILE; tb < nf; tb += (int64_t)gridDim.x * TILE) {
     const int64_t i = tb + wv * VPW + sub;
     if (i >= nf) continue;

@@ -42,6 +42,7 @@ __global__ __launch_bounds__(kBlock) void k_td_expand(
         if constexpr (DIFF) {
           // osnap: the old row of a vertex first visited at the previous (first, unfilled) pull
           // level was never written: it is all zero (see start_batch)
+          // (written out, not own_row: the helper changes these kernels' register counts)
           const V<VW> old =
               (osnap && !any_visited(osnap, u)) ? vzero<VW>() : ldv<VW>(fsrc + uo);
 #pragma unroll
@@ -171,13 +172,12 @@ __global__ void k_batch_seed(Ctr* c0, uint32_t nf, unsigned long long ef, const 
 // top-down finalize: new = acc & ~vis; update both visited buffers; build the next frontier.
 // FUSE: the level's new-bit counts go straight to this block's counter-slab row (as in the
 // bottom-up kernels) instead of a k_count_frontier pass over the new frontier.
-template <int W, bool COUNT, bool FUSE>
+template <int W, bool FUSE>
 __global__ __launch_bounds__(kBlock) void k_td_finalize(
     const int32_t* touched, const int64_t* rowptr, uint64_t* visCur, uint64_t* visOld,
     uint64_t* accNext, const uint64_t* alive, const uint64_t* gmask, uint32_t* done, int32_t* fl2,
     Ctr* ctr, const int32_t* fl_old, int64_t nf_old_arg, const uint32_t* nfold_dev,
     uint64_t* accCur_zero, uint32_t* anyvis, uint32_t* slabF, int lazy, const uint32_t* stop) {
-  static_assert(!(FUSE && COUNT), "the edge-counting pass uses k_count_frontier");
   if (stop && *stop) {  // the batch stopped at this level (k_td_expand_small)
     if constexpr (FUSE)
       for (int i = threadIdx.x; i < 64 * W; i += kBlock) slabF[(size_t)blockIdx.x * 64 * W + i] = 0u;
@@ -188,29 +188,22 @@ __global__ __launch_bounds__(kBlock) void k_td_finalize(
   constexpr int VW = L::VW, G = L::G, VPW = L::VPW, TILE = L::TILE;
   __shared__ LdsQueue q;
   __shared__ unsigned long long scratch[kWaves];
-  constexpr int CR = 65;  // bank-skewed counter rows (see BitCounter::spill_strided)
-  __shared__ uint32_t cnt[FUSE ? CR * W : 1];
-  if constexpr (FUSE)
-    for (int i = threadIdx.x; i < CR * W; i += kBlock) cnt[i] = 0;
-  q_init(q);
-  __syncthreads();
-  BitCounter<VW> bc;
-  int nadd = 0;
-  if constexpr (FUSE) bc.zero();
-  const int64_t nt = ctr->touched.v;  // written by k_td_expand (previous kernel on the stream)
   const int lane = lane_id(), slot = lane % G, sub = lane / G;
   const int wv = threadIdx.x >> 6;
-  V<VW> am, gm;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) {
-    am.w[j] = alive[slot * VW + j];
-    gm.w[j] = gmask[slot * VW + j];
-  }
+  using Counts = GroupCounts<W, 6, 65, false>;  // bank-skewed counter rows (see spill_strided)
+  __shared__ uint32_t cnt[FUSE ? Counts::kLdsWords : 1];
+  Counts gc(cnt, slot);
+  if constexpr (FUSE) gc.zero(kBlock);
+  q_init(q);
+  __syncthreads();
+  const int64_t nt = ctr->touched.v;  // written by k_td_expand (previous kernel on the stream)
+  const V<VW> am = alive_mask<VW>(alive, gmask, slot);
   unsigned long long ef = 0, ev = 0;
   for (int64_t tb = (int64_t)blockIdx.x * TILE; tb < nt; tb += (int64_t)gridDim.x * TILE) {
     const int64_t idx = tb + wv * VPW + sub;
     const bool valid = idx < nt;
     int32_t v = 0;
+    // (own new bits: whatever was pushed and the row misses, alive or not)
     bool anynew = false, notfull = false, rnz = false;
     V<VW> nw = vzero<VW>();
     uint32_t deg = 0;
@@ -219,14 +212,14 @@ __global__ __launch_bounds__(kBlock) void k_td_finalize(
       const int64_t vo = (int64_t)v * W + slot * VW;
       const V<VW> a = ldv<VW>(accNext + vo);
       // lazy: a vertex no group has visited yet may have a stale row (see k_zero_part_rows)
-      const V<VW> r = (lazy && !any_visited(anyvis, v)) ? vzero<VW>() : ldv<VW>(visCur + vo);
+      const V<VW> r = own_row<VW>(visCur, lazy ? anyvis : nullptr, v, vo);
       V<VW> nv;
 #pragma unroll
       for (int j = 0; j < VW; ++j) {
         nw.w[j] = a.w[j] & ~r.w[j];
         nv.w[j] = r.w[j] | nw.w[j];
         anynew |= nw.w[j] != 0;
-        notfull |= (~nv.w[j] & am.w[j] & gm.w[j]) != 0;
+        notfull |= (~nv.w[j] & am.w[j]) != 0;
         rnz |= r.w[j] != 0;
       }
       stv<VW>(accNext + vo, nw);
@@ -234,13 +227,8 @@ __global__ __launch_bounds__(kBlock) void k_td_finalize(
       stv<VW>(visOld + vo, nv);
       deg = (uint32_t)(rowptr[v + 1] - rowptr[v]);
     }
-    if constexpr (FUSE) {  // nw is zero for invalid lanes
-      bc.add(nw);
-      if (++nadd == (1 << BitCounter<VW>::D) - 1) {
-        bc.template spill_strided<CR>(cnt, slot);
-        nadd = 0;
-      }
-    }
+    if constexpr (FUSE) gc.add(nw);  // (zero for invalid lanes)
+    // (own epilogue: plain per-vertex atomics, and a push level keeps no active lists)
     const uint64_t bn = __ballot(anynew), bf = __ballot(notfull), br = __ballot(rnz);
     const bool g_new = (bn >> (sub * G)) & L::GBITS;
     const bool g_full = !((bf >> (sub * G)) & L::GBITS);
@@ -259,12 +247,7 @@ __global__ __launch_bounds__(kBlock) void k_td_finalize(
   q_flush(q, fl2, &ctr->fl2.v, 0, true);
   block_sum_add(ef, &ctr->ef2.v, scratch);
   block_sum_add(ev, &ctr->ev2.v, scratch);
-  if constexpr (FUSE) {
-    bc.template spill_strided<CR>(cnt, slot);
-    __syncthreads();
-    uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-    for (int i = threadIdx.x; i < 64 * W; i += kBlock) row[i] = cnt[i + (i >> 6)];
-  }
+  if constexpr (FUSE) gc.store(slabF, kBlock);
   // zero the consumed top-down frontier bits of the previous frontier
   if (accCur_zero) {
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -312,24 +295,20 @@ __global__ __launch_bounds__(kBlock) void k_td_fused(
   static_assert(TILE * U <= QC / 2, "queue room for one step");
   __shared__ LdsQueueN<QC> q;
   __shared__ unsigned long long scratch[kWaves];
-  constexpr int CR = 65;  // bank-skewed counter rows (see BitCounter::spill_strided)
-  __shared__ uint32_t cnt[CR * W];
+  using Counts = GroupCounts<W, 6, 65, false>;  // bank-skewed counter rows (see spill_strided)
+  __shared__ uint32_t cnt[Counts::kLdsWords];
   // bitmap mode: words per tile (8192 ids; 4096-id tiles measured 6 % slower on the road grid)
   constexpr int BW = kBlock;
   __shared__ uint16_t lst[BW * 32];  // bitmap mode: set bits of the tile's words
   __shared__ uint32_t wsum[kWaves];
-  for (int i = threadIdx.x; i < CR * W; i += kBlock) cnt[i] = 0;
-  q_init(q);
-  __syncthreads();
-  BitCounter<VW> bc;
-  bc.zero();
-  int nadd = 0;
-  const int64_t nf = (int64_t)*nf_dev;
   const int lane = lane_id(), slot = lane % G, sub = lane / G;
   const int wv = threadIdx.x >> 6;
-  V<VW> amg;
-#pragma unroll
-  for (int j = 0; j < VW; ++j) amg.w[j] = alive[slot * VW + j] & gmask[slot * VW + j];
+  Counts gc(cnt, slot);
+  gc.zero(kBlock);
+  q_init(q);
+  __syncthreads();
+  const int64_t nf = (int64_t)*nf_dev;
+  const V<VW> amg = alive_mask<VW>(alive, gmask, slot);
   unsigned long long ef = 0, ev = 0, ef_own = 0;
   // direction check inside the batch (the host's test, on this frontier's degree sum estimated
   // from its size and the previous frontier's mean degree): a level the host would run as a pull
@@ -432,11 +411,7 @@ __global__ __launch_bounds__(kBlock) void k_td_fused(
             if (fresh) ev += deg;
           }
         }
-        bc.add(nw);
-        if (++nadd == (1 << BitCounter<VW>::D) - 1) {
-          bc.template spill_strided<CR>(cnt, slot);
-          nadd = 0;
-        }
+        gc.add(nw);
         q_push(q, app, x);
       }
       q_flush(q, flNext, &ctr->fl2.v, TILE * U, false);
@@ -490,10 +465,7 @@ __global__ __launch_bounds__(kBlock) void k_td_fused(
   if (tail) block_sum_add(ef, &ctr->ef2.v, scratch);
   if (own) block_sum_add(ef_own, &cprev->ef2.v, scratch);
   block_sum_add(ev, &ctr->ev2.v, scratch);
-  bc.template spill_strided<CR>(cnt, slot);
-  __syncthreads();
-  uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-  for (int i = threadIdx.x; i < 64 * W; i += kBlock) row[i] = cnt[i + (i >> 6)];
+  gc.store(slabF, kBlock);
 }
 
 }  // namespace bp

@@ -30,7 +30,9 @@
 // wave-instruction slice.
 //
 // Source layout (one class, five translation units that compile in parallel):
-//   bitpar/common.hpp  init.hpp  push.hpp  pull.hpp  hybrid.hpp   kernels by family
+//   bitpar/bits.hpp                      pure bit helpers (HIP-free, pinned by the host self-test)
+//   bitpar/common.hpp  init.hpp  push.hpp  hybrid.hpp  tiles.hpp      kernels by family; the pull
+//   bitpar/pull.hpp  pull_full.hpp  pull_lists.hpp  pull_tail.hpp     levels': pulls, lists, tail push
 //   bitpar_solver.hip  construction, batches, the level loop (direction choice, reductions)
 //   bitpar_push.hip    top-down levels and the device-driven level batches
 //   bitpar_pull.hip    bottom-up levels (prefix pull + tail push, narrow / lean / chunk pulls),
@@ -70,7 +72,7 @@ inline void load_code_objects(hipStream_t s) {
   load_code_tiles(s);
 }
 
-struct ChunkDesc;  // (bitpar/pull.hpp)
+struct ChunkDesc;  // (bitpar/pull_lists.hpp)
 
 class BitparSolver final : public Solver {
  public:
@@ -241,8 +243,10 @@ class BitparSolver final : public Solver {
     const uint32_t* dprobe = nullptr;  // (k_bu_full)
     int flags = 0;
   };
-  template <class K>
-  void launch_narrow(K k, int grid, int block, const PullArgs& a, hipStream_t s);
+  // (Cfg: a k_bu_narrow variant, bitpar/pull.hpp; p: the level's plan, whose launch shape the
+  // variant must have)
+  template <int W, class Cfg>
+  void launch_narrow(int grid, const PullArgs& a, hipStream_t s, const PullPlan* p = nullptr);
   template <class K>
   void launch_full(K k, int grid, const PullArgs& a, hipStream_t s);
   template <int W, bool COUNT>

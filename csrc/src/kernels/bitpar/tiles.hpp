@@ -162,16 +162,20 @@ __global__ __launch_bounds__(kTileBlock, 1) void k_pfx_tiles(
   constexpr int NWV = kTileBlock / 64;
   constexpr int PB = 4;       // rows in flight per lane group and batch
   constexpr int Q = kRoundQ;
-  constexpr int CR = 65;      // bank-skewed counter rows (BitCounter::spill_strided)
   constexpr int YW = VT * W + 64;  // + one dummy word per lane (idle lanes' ORs, no conflicts)
   __shared__ uint32_t hub[kTileHubW];
   __shared__ unsigned long long Y[NWV][YW];
   __shared__ uint32_t lst[NWV][kRound];
-  __shared__ uint32_t cnt[CR * W];
-  for (int i = threadIdx.x; i < kTileHubW; i += kTileBlock) hub[i] = pvis[i];
-  for (int i = threadIdx.x; i < CR * W; i += kTileBlock) cnt[i] = 0;
-  __syncthreads();
   const int lane = lane_id(), slot = lane % G, sub = lane / G, wv = threadIdx.x >> 6;
+  // 5 slices: a spill (one LDS add per set counter bit, ~100 per lane at level 2) every 31
+  // passes (6 slices do not fit the 128 VGPRs of a 1024-thread block at 16 words);
+  // bank-skewed counter rows (spill_strided), 32-bit halves (spill_strided32)
+  using Counts = GroupCounts<W, 5, 65, true>;
+  __shared__ uint32_t cnt[Counts::kLdsWords];
+  Counts gc(cnt, slot);
+  for (int i = threadIdx.x; i < kTileHubW; i += kTileBlock) hub[i] = pvis[i];
+  gc.zero(kTileBlock);
+  __syncthreads();
   unsigned long long* y = Y[wv];
   const int dummy = VT * W + lane;
   uint32_t* ls = lst[wv];
@@ -188,11 +192,6 @@ __global__ __launch_bounds__(kTileBlock, 1) void k_pfx_tiles(
     wev[threadIdx.x] = 0;
     wnf[threadIdx.x] = 0;
   }
-  // 5 slices: a spill (one LDS add per set counter bit, ~100 per lane at level 2) every 31
-  // passes (6 slices do not fit the 128 VGPRs of a 1024-thread block at 16 words)
-  BitCounter<VW, 5> bc;
-  bc.zero();
-  int nadd = 0;
   const int64_t nwaves = (int64_t)gridDim.x * NWV;
   auto load_round = [&](const TileRound& r, uint32_t (&pk)[Q]) {
 #pragma unroll
@@ -361,6 +360,7 @@ __global__ __launch_bounds__(kTileBlock, 1) void k_pfx_tiles(
             for (int j = 0; j < VW; ++j) pushed |= pa[k].w[j] != 0;
             if (ACC && pushed) stv<VW>(acc + (int64_t)v * W + slot * VW, vzero<VW>());
           }
+          // (new_bits() written out: the helper costs this kernel a VGPR at 16 words)
           V<VW> nw, nvr;
           bool anynew = false, notfull = false, rnz = false;
 #pragma unroll
@@ -373,11 +373,7 @@ __global__ __launch_bounds__(kTileBlock, 1) void k_pfx_tiles(
             rnz |= r.w[j] != 0;
           }
           if (put) stv<VW>(O + (int64_t)v * W + slot * VW, nvr);
-          bc.add(nw);
-          if (++nadd == (1 << decltype(bc)::D) - 1) {
-            bc.template spill_strided32<CR>(cnt, slot);
-            nadd = 0;
-          }
+          gc.add(nw);
           // per-group flags (a group's lanes share validity; the others OR over its words),
           // compressed to one bit per group = per vertex of the pass
           const uint32_t gval = group_any<G>(__ballot(valid));
@@ -413,8 +409,7 @@ __global__ __launch_bounds__(kTileBlock, 1) void k_pfx_tiles(
 #pragma unroll
     for (int q = 0; q < Q; ++q) pkc[q] = pkb[q];
   }
-  bc.template spill_strided32<CR>(cnt, slot);
-  __syncthreads();
+  gc.store(slabF, kTileBlock);  // (its barrier also orders the waves' sums below)
   if (threadIdx.x == 0) {
     uint32_t a = 0;
     unsigned long long b = 0, c = 0;
@@ -427,8 +422,6 @@ __global__ __launch_bounds__(kTileBlock, 1) void k_pfx_tiles(
     if (b) atomicAdd(&ctr->ef2.v, b);
     if (c) atomicAdd(&ctr->ev2.v, c);
   }
-  uint32_t* row = slabF + (size_t)blockIdx.x * (64 * W);
-  for (int i = threadIdx.x; i < 64 * W; i += kTileBlock) row[i] = cnt[i + (i >> 6)];
 }
 
 // frontier list from the frontier bitmap (LDS block queue; rare: only when a top-down level

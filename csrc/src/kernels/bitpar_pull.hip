@@ -216,9 +216,13 @@ PlanLevel BitparSolver::plan_level(const Loop& S) const {
   return l;
 }
 
-template <class K>
-void BitparSolver::launch_narrow(K k, int grid, int block, const PullArgs& a, hipStream_t s) {
-  k<<<grid, block, 0, s>>>(a.list, a.nact, g_.rowptr, g_.col, a.R, a.O, a.alive, small().gmask,
+template <int W, class Cfg>
+void BitparSolver::launch_narrow(int grid, const PullArgs& a, hipStream_t s, const PullPlan* p) {
+  // the plan states the launch shape (PullPlan::block / minw / hub_w), the variant has it built
+  // in: they must agree
+  if (p && (p->block != Cfg::BT || p->minw != Cfg::MINW || p->hub_w != Cfg::HUBW))
+    fail("k_bu_narrow: the variant's launch shape is not the plan's");
+  k_bu_narrow<W, Cfg><<<grid, Cfg::BT, 0, s>>>(a.list, a.nact, g_.rowptr, g_.col, a.R, a.O, a.alive, small().gmask,
                            done_.as<uint32_t>(), a.act2, a.fl2, a.ctr, anyvis_.as<uint32_t>(),
                            a.filter_from, a.actw2, std::max(opt.wide_degree, kWideLater), a.slab,
                            a.pacc, a.stamp, a.epoch, a.plen, a.nact_dev, a.snap, a.gate);
@@ -309,6 +313,7 @@ void BitparSolver::bu_tail_push(Loop& S, BuLevel& L, hipStream_t s) {
 template <int W, bool COUNT>
 void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
   using Lw = Lay<W>;
+  // (the edge-counting pass counts with k_count_frontier: nothing fused there)
   constexpr bool FUSE = !COUNT;
   const PullPlan& p = L.p;
   if (p.kind == PullKind::Tiled) {
@@ -335,27 +340,21 @@ void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
   const int gn = grid_for(S.nact, Lw::TILE, kMaxGrid);  // (the 256-thread kernels)
   switch (p.kind) {
     case PullKind::Prefix: {
-      constexpr int BT = pfx_block(W);
-      const int g = grid_for(S.nact, (BT / 64) * Lw::VPW, 512);
-      // 4-neighbour steps: 122 VGPRs, no spills (8-neighbour steps spilled at the 128-VGPR
-      // bound): RMAT-26 5.17 -> 4.96 ms (the full pulls of level 3 keep 8: 5.8 vs 6.8 ms)
-      // (FBM: frontier bitmap in place of the list, see PullPlan::fbm_out)
-      auto kn = FUSE ? k_bu_narrow<W, COUNT, BT, kHubW, FUSE, true, true, 4, 0, pfx_minw(W), true>
-                     : k_bu_narrow<W, COUNT, BT, kHubW, false, true, true>;
-      if (FUSE) a.fl2 = reinterpret_cast<int32_t*>(fbm_tile_.p);
+      using Cfg = NarrowPrefix<W, FUSE>;
+      const int g = grid_for(S.nact, (Cfg::BT / 64) * Lw::VPW, 512);
+      if (Cfg::FBM) a.fl2 = reinterpret_cast<int32_t*>(fbm_tile_.p);
       a.pacc = acc_[S.ac].as<uint64_t>();
       a.stamp = p.pfx_nostamp ? nullptr : stamp_.as<int32_t>();
       a.epoch = epoch_;
       a.plen = L.plen;
-      launch_narrow(kn, g, BT, a, s);
+      launch_narrow<W, Cfg>(g, a, s, &p);
       if (FUSE) L.rows += g;
       break;
     }
     case PullKind::Hub: {
-      constexpr int BT = 1024;
-      const int g = grid_for(S.nact, (BT / 64) * Lw::VPW, 512);
-      launch_narrow(p.hub_big ? k_bu_narrow<W, COUNT, BT, kHubBig, FUSE>
-                              : k_bu_narrow<W, COUNT, BT, kHubW, FUSE>, g, BT, a, s);
+      const int g = grid_for(S.nact, (NarrowHub<FUSE>::BT / 64) * Lw::VPW, 512);
+      if (p.hub_big) launch_narrow<W, NarrowHubBig<FUSE>>(g, a, s, &p);
+      else launch_narrow<W, NarrowHub<FUSE>>(g, a, s, &p);
       if (FUSE) L.rows += g;
       break;
     }
@@ -375,7 +374,8 @@ void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
       a.dprobe = L.dsnap;
       a.flags = p.skip_now ? kFlagSkipRows : 0;
       if (p.full) launch_full(k_bu_full<W, full_cs<W>(), 1>, go, a, s);
-      else launch_narrow(k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false, false, 8, 1>, go, kBlock, a, s);
+      else if constexpr (FUSE) launch_narrow<W, NarrowShort1<true>>(go, a, s, &p);
+      else fail("the lean pass is not planned for an edge-counting run");
       L.rows += go;
       break;
     }
@@ -388,12 +388,14 @@ void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
       break;
     }
     default: {
-      auto kn = FUSE ? (p.filter ? k_bu_narrow<W, COUNT, kBlock, 0, FUSE, true>
-                         : p.short1 ? k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false, false, 8, 1>
-                                    : k_bu_narrow<W, COUNT, kBlock, 0, FUSE, false>)
-                     : (p.filter ? k_bu_narrow<W, COUNT, kBlock, 0, false, true>
-                                 : k_bu_narrow<W, COUNT, kBlock, 0, false, false>);
-      launch_narrow(kn, gn, kBlock, a, s);
+      // (the short first step only where the counts are fused: no NarrowShort1<false> exists)
+      bool short1 = false;
+      if constexpr (FUSE) {
+        short1 = !p.filter && p.short1;
+        if (short1) launch_narrow<W, NarrowShort1<true>>(gn, a, s, &p);
+      }
+      if (p.filter) launch_narrow<W, NarrowFiltered<FUSE>>(gn, a, s, &p);
+      else if (!short1) launch_narrow<W, NarrowPlain<FUSE>>(gn, a, s, &p);
       if (FUSE) L.rows += gn;
     }
   }
@@ -462,7 +464,7 @@ void BitparSolver::bu_wide(Loop& S, BuLevel& L, hipStream_t s) {
     bu_chunks<W>(S, L, d, offs_.as<int64_t>() + S.nactw - 1, chunks_max, s);
   }
   const int gw = grid_for(S.nactw, Lw::TILE, kMaxGrid);
-  auto kw = p.fbm_out ? k_bu_wide_finalize<W, COUNT, FUSE, true> : k_bu_wide_finalize<W, COUNT, FUSE>;
+  auto kw = p.fbm_out ? k_bu_wide_finalize<W, FUSE, true> : k_bu_wide_finalize<W, FUSE>;
   kw<<<gw, kBlock, 0, s>>>(
       lw, S.nactw, g_.rowptr, L.R, L.O, acc_[S.ac].as<uint64_t>(), L.alive, L.sm.gmask,
       done_.as<uint32_t>(), actw_[1].as<int32_t>(), fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
@@ -565,7 +567,6 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
   const uint32_t level0 = S.level;
   const auto t0 = std::chrono::steady_clock::now();
   trace::Range range_batch("bitpar L%u-%u BU batch", level0 + 1, level0 + K);
-  auto kn = k_bu_narrow<W, false, kBlock, 0, true, false, false, 8, 1>;
   const bool full = full_pull();
   // dskip: after a skipping level the batch's levels probe the snapshot (taken once, before the
   // first of them); they skip nothing themselves
@@ -579,7 +580,7 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
     a.gate = gate;
     a.dprobe = dsnap;
     if (full) launch_full(k_bu_full<W, full_cs<W>(), 1>, grid, a, s);
-    else launch_narrow(kn, grid, kBlock, a, s);
+    else launch_narrow<W, NarrowShort1<true>>(grid, a, s);
   };
   for (int i = 0; i < K; ++i) {
     const BuGate gate{slots + i, opt.beta, alpha, i == 0 ? 1 : 0};

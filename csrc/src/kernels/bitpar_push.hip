@@ -58,7 +58,7 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
   const int64_t nt_max = std::min<int64_t>(std::max<int64_t>(S.ef, S.nf), n);
   const int gf = grid_for(nt_max, L::TILE, grid);
   constexpr bool FUSE = !COUNT;  // counts fused into finalize (the edge-count pass: k_count_frontier)
-  k_td_finalize<W, COUNT, FUSE><<<gf, kBlock, 0, s>>>(
+  k_td_finalize<W, FUSE><<<gf, kBlock, 0, s>>>(
       touched_.as<int32_t>(), g_.rowptr, R, O, acc_[S.ac ^ 1].as<uint64_t>(), alive,
       sm.gmask, done_.as<uint32_t>(), fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
       fl_[S.fc].as<int32_t>(), S.nf, nullptr,
@@ -187,7 +187,7 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
           done_.as<uint32_t>(), acc_[S.ac ^ 1].as<uint64_t>(), stamp_.as<int32_t>(), epoch_,
           touched_.as<int32_t>(), cur, S.lazy ? anyvis_.as<uint32_t>() : nullptr,
           S.osnap_next ? asnap_.as<uint32_t>() : nullptr, i > 0 ? prev : nullptr, ef_stop_for(level));
-    k_td_finalize<W, COUNT, FUSE><<<grid, kBlock, 0, s>>>(touched_.as<int32_t>(), g_.rowptr, R, O,
+    k_td_finalize<W, FUSE><<<grid, kBlock, 0, s>>>(touched_.as<int32_t>(), g_.rowptr, R, O,
                                acc_[S.ac ^ 1].as<uint64_t>(), aslot + 16 * aidx, sm.gmask,
                                done_.as<uint32_t>(), fl_[S.fc ^ 1].as<int32_t>(), cur,
                                fl_[S.fc].as<int32_t>(), 0, &prev->fl2.v,

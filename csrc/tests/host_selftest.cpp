@@ -16,6 +16,7 @@
 #include <unistd.h>
 
 #include "../cli/thread_group.hpp"
+#include "../src/kernels/bitpar/bits.hpp"
 #include "../src/kernels/bitpar/pull_plan.hpp"
 #include "msbfs/graph.hpp"
 
@@ -373,6 +374,97 @@ static void tuning() {
 }
 }  // namespace plan_test
 
+// ---- the kernels' pure bit helpers (bitpar/bits.hpp), on hand-written cases
+namespace bits_test {
+using namespace msbfs::bp;
+
+static void new_bits_cases() {
+  const uint64_t ALL = ~0ull;
+  {  // empty row: everything pulled among the alive groups is new, and it is a first visit
+    const V<1> r{{0}}, acc{{0x0F0Full}}, am{{0x00FFull}};
+    const NewBits<1> o = new_bits(r, acc, am);
+    CHECK(o.nw.w[0] == 0x000Full && o.nv.w[0] == 0x000Full);
+    CHECK(o.anynew && o.notfull && !o.rnz);  // (alive groups 4-7 still missing)
+    const NewBits<1> none = new_bits(r, V<1>{{0}}, am);
+    CHECK(none.nw.w[0] == 0 && none.nv.w[0] == 0 && !none.anynew && none.notfull && !none.rnz);
+  }
+  {  // full row: nothing new, nothing missing, whatever was pulled
+    const V<1> r{{ALL}}, acc{{0x1234ull}}, am{{ALL}};
+    const NewBits<1> o = new_bits(r, acc, am);
+    CHECK(o.nw.w[0] == 0 && o.nv.w[0] == ALL && !o.anynew && !o.notfull && o.rnz);
+    // full on the alive groups only: the same, and the row keeps its dead groups' bits
+    const NewBits<1> p = new_bits(V<1>{{0xFF0Full}}, V<1>{{0x00F0ull}}, V<1>{{0x000Full}});
+    CHECK(p.nw.w[0] == 0 && p.nv.w[0] == 0xFF0Full && !p.anynew && !p.notfull && p.rnz);
+  }
+  {  // acc outside am: bits of groups that are not alive are dropped
+    const V<1> r{{0x1ull}}, acc{{0xF0ull}}, am{{0x0Full}};
+    const NewBits<1> o = new_bits(r, acc, am);
+    CHECK(o.nw.w[0] == 0 && o.nv.w[0] == 0x1ull && !o.anynew && o.notfull && o.rnz);
+    const NewBits<1> q = new_bits(r, V<1>{{0xF6ull}}, am);  // (bits 1, 2 inside)
+    CHECK(q.nw.w[0] == 0x6ull && q.nv.w[0] == 0x7ull && q.anynew && q.notfull && q.rnz);
+    const NewBits<1> f = new_bits(r, V<1>{{0xFEull}}, am);  // (completes the alive groups)
+    CHECK(f.nw.w[0] == 0xEull && f.nv.w[0] == 0xFull && f.anynew && !f.notfull);
+  }
+  {  // one word of two: the flags OR over the words, the words stay apart
+    const V<2> r{{0, 0x3ull}}, acc{{0, 0xCull}}, am{{0x1ull, 0xFull}};
+    const NewBits<2> o = new_bits(r, acc, am);
+    CHECK(o.nw.w[0] == 0 && o.nw.w[1] == 0xCull && o.nv.w[0] == 0 && o.nv.w[1] == 0xFull);
+    CHECK(o.anynew && o.notfull && o.rnz);  // (word 0 misses its one alive group)
+    const NewBits<2> p = new_bits(r, V<2>{{0x1ull, 0xCull}}, am);
+    CHECK(p.nw.w[0] == 0x1ull && p.nw.w[1] == 0xCull && p.anynew && !p.notfull && p.rnz);
+    const NewBits<2> z = new_bits(V<2>{{0, 0}}, V<2>{{0, 0x8ull}}, am);
+    CHECK(z.nw.w[1] == 0x8ull && z.anynew && z.notfull && !z.rnz);
+    // gained() on the precomputed missing groups is the same function
+    const V<2> unv = missing(r, am);
+    CHECK(unv.w[0] == 0x1ull && unv.w[1] == 0xCull);
+    const NewBits<2> g = gained(r, acc, unv);
+    CHECK(g.nw.w[1] == o.nw.w[1] && g.nv.w[1] == o.nv.w[1] && g.notfull == o.notfull);
+  }
+}
+
+// after 2^D - 1 adds of random words every count equals the number of adds with that bit set
+template <int D>
+static void bit_counter_case(uint64_t seed) {
+  constexpr int VW = 2, N = (1 << D) - 1;
+  BitCounter<VW, D> bc;
+  bc.zero();
+  uint32_t want[VW][64] = {};
+  for (int i = 0; i < N; ++i) {
+    V<VW> x;
+    for (int j = 0; j < VW; ++j) {
+      x.w[j] = msbfs::mix64(seed + (uint64_t)(i * VW + j));
+      if (i % 7 == 3) x.w[j] = ~0ull;  // (some full words: the carries run through every slice)
+      for (int b = 0; b < 64; ++b) want[j][b] += (uint32_t)((x.w[j] >> b) & 1ull);
+    }
+    bc.add(x);
+  }
+  bool ok = true, any_ok = true;
+  for (int j = 0; j < VW; ++j) {
+    uint64_t nz = 0;
+    for (int b = 0; b < 64; ++b) {
+      ok &= bc.count(j, b) == want[j][b];
+      if (want[j][b]) nz |= 1ull << b;
+    }
+    any_ok &= bc.any(j) == nz;
+  }
+  CHECK(ok);
+  CHECK(any_ok);
+  bc.zero();
+  CHECK(bc.any(0) == 0 && bc.any(1) == 0 && bc.count(1, 63) == 0);
+}
+
+static void bit_counter_cases() {
+  bit_counter_case<5>(11);
+  bit_counter_case<6>(12);
+  bit_counter_case<7>(13);
+  // every add with all bits set: the count saturates the D slices exactly at 2^D - 1
+  BitCounter<1, 5> bc;
+  bc.zero();
+  for (int i = 0; i < 31; ++i) bc.add(V<1>{{~0ull}});
+  CHECK(bc.count(0, 0) == 31 && bc.count(0, 63) == 31);
+}
+}  // namespace bits_test
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp";
   const std::string gp = dir + "/selftest_g.bin", qp = dir + "/selftest_q.bin";
@@ -381,6 +473,8 @@ int main(int argc, char** argv) {
   plan_test::cases();
   plan_test::batches();
   plan_test::tuning();
+  bits_test::new_bits_cases();
+  bits_test::bit_counter_cases();
   // generators: threaded == serial
   EdgeList e1 = gen_rmat(12, 8, 5, 0.57, 0.19, 0.19, true, 1);
   EdgeList e8 = gen_rmat(12, 8, 5, 0.57, 0.19, 0.19, true, T);

@@ -443,6 +443,48 @@ def test_bitpar_lean_and_lazy_paths(msbfs_pkg, knobs):
         assert not any("l" in k for k in kinds), kinds
 
 
+@pytest.fixture(scope="module")
+def epilogue_graph(msbfs_pkg):
+    """relabelled RMAT of scale 14 on the device + its host copy in the original ids"""
+    dg = msbfs_pkg.DeviceGraph.rmat(14, 16, 5, device=0)
+    hg = dg.download()  # (before relabelling: the queries and F speak the original ids)
+    dg.relabel_by_degree()
+    yield dg, hg
+    dg.close()
+
+
+@pytest.mark.parametrize("K", [64, 128, 256, 512, 1024])
+def test_bitpar_pull_epilogue_every_lane_layout(msbfs_pkg, epilogue_graph, K):
+    """The pull kernels' shared vertex epilogue and group counters at every lane layout (1, 2, 4,
+    8, 16 words: K groups of 4 sources) on a relabelled RMAT of scale 14: the full pull (kind f),
+    the lean first-row pass with its overflow pull (l, tuning lean_min=0) and the narrow pull on
+    the late levels (n, tuning full=0), with most vertices on the wide list (wide degree 4: chunk
+    pulls + wide finalize) and at the default threshold, plain and edge-counting. F (and the edge
+    sums) equal the CPU oracle on two runs of a reused solver; the plain runs' level traces hold
+    the kind each tuning is there for; an edge-counting run never takes f or l (its counts come
+    from the count pass, so it keeps the narrow pull): there only full=0's late levels are
+    asserted."""
+    m = msbfs_pkg
+    dg, hg = epilogue_graph
+    qs = m.QuerySet.random(hg.n, K, 4, seed=K + 3)
+    ref = m.cpu_bfs(hg, qs, count_edges=True)
+    for tun in ({}, {"lean_min": 0}, {"full": 0}):
+        for wide in (4, None):
+            kw = {} if wide is None else {"wide_degree": wide}
+            for count in (False, True):
+                with m.Solver(dg, "bitpar", max_groups=K, tuning=tun, **kw) as s:
+                    for rep in range(2):
+                        r = s.run(qs, count_edges=count)
+                        assert np.array_equal(r.F, ref.F), (K, tun, wide, count, rep)
+                        if count:
+                            assert np.array_equal(r.edges, ref.edges), (K, tun, wide, rep)
+                    pulls = [t["kind"] for t in s.level_trace() if t["dir"] == "B"]
+                if "full" in tun:  # late levels: from the third pull level on
+                    assert len(pulls) > 2 and set(pulls[2:]) == {"n"}, (K, wide, count, pulls)
+                elif not count:
+                    assert ("l" if "lean_min" in tun else "f") in pulls, (K, wide, pulls)
+
+
 @pytest.mark.parametrize("tun", [{"bu_max": 1 << 30}, {"bu_max": 1 << 30, "batch": 2},
                                  {"bu_max": 1 << 30, "batch": 3, "lean": 0}])
 def test_bitpar_device_pull_batches(msbfs_pkg, tun):
