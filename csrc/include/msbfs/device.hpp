@@ -144,6 +144,16 @@ class Solver {
   // of reached vertices, i.e. 2x the Graph500 traversed-edge count) are written to host memory.
   virtual void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
                    int64_t* edges2, RunStats* st, hipStream_t stream) = 0;
+  // run() plus the per-vertex distances: dist_dev[k * ld + v] (device memory, K x ld int32,
+  // ld >= n) = BFS level of vertex v (the user's id, also on relabelled graphs) from group k, 0
+  // for its valid sources, -1 where unreached. Columns [0, n) of every row are written (a group
+  // without a valid source gives a row of -1), columns [n, ld) are never touched.
+  // The reached (>= 0) entries of row k sum to F[k].
+  virtual void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                        int32_t* dist_dev, int64_t ld, RunStats* st, hipStream_t stream) {
+    (void)K, (void)qoff, (void)qids, (void)F, (void)dist_dev, (void)ld, (void)st, (void)stream;
+    fail("distance output is not supported by this solver");
+  }
   // Groups one solver pass handles at once (bit-parallel: 64*W; per-group solvers run any
   // number in one call). Callers that overlap work between passes split runs at this size.
   virtual int64_t pass_groups() const { return INT64_MAX; }

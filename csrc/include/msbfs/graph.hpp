@@ -94,9 +94,11 @@ QuerySet gen_queries(int64_t n, int64_t K, int64_t size, uint64_t seed);
 int64_t cpu_msbfs_F(const HostCsr& g, const int32_t* src, int64_t nsrc, std::vector<int32_t>& dist,
                     std::vector<int64_t>& queue, int64_t* edges = nullptr,
                     int32_t* levels = nullptr);
-// All groups, query-parallel over nthreads host threads.
+// All groups, query-parallel over nthreads host threads. dist_out != nullptr: row k of it (ld >= n
+// elements apart) gets group k's distances, -1 for unreached vertices; columns [n, ld) stay.
 void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
-                   std::vector<int64_t>* edges, int nthreads);
+                   std::vector<int64_t>* edges, int nthreads, int32_t* dist_out = nullptr,
+                   int64_t ld = 0);
 
 // Reference tie-break (main.cu:381-397): first valid F, then strict '<'; returns -1 if K==0.
 int64_t argmin_first(const std::vector<int64_t>& F);

@@ -85,6 +85,13 @@ int msbfs_cpu_run(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t 
                   const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges,
                   int nthreads);
 
+/* The same plus the per-vertex distances: dist[k*ld + v] (K x ld int32, ld >= n) = BFS level of
+ * vertex v from group k, 0 for its valid sources, -1 where unreached; columns [n, ld) of every
+ * row are left as they are. The reached entries of row k sum to F[k]. */
+int msbfs_cpu_run_dist(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
+                       const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist,
+                       int64_t ld, int nthreads);
+
 /* ---- device graphs ---- */
 int msbfs_graph_from_host_csr(int device, int64_t n, const int64_t* rowptr, const int32_t* col,
                               msbfs_graph* out);
@@ -133,6 +140,26 @@ int msbfs_solver_prepare_hybrid(msbfs_solver s, int part, int nparts, void* stre
  * traversed-edge count). stream = hipStream_t or NULL for the null stream. */
 int msbfs_solver_run(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
                      int64_t* F, int64_t* edges2, msbfs_stats* st, void* stream);
+/* Per-vertex distances for every group, from every solver. dist[k*ld + v] is int32, v in the
+ * ORIGINAL vertex ids (also on relabelled graphs): 0 for the valid sources of group k (ids
+ * outside [0, n) are dropped, duplicates are harmless), the BFS level for reached vertices, -1
+ * for unreached ones; an empty group or one without a valid source gives a row of -1. The solver
+ * writes columns [0, n) of every row (including the -1 fill) and never touches columns
+ * [n, ld); ld >= n. F is returned as by msbfs_solver_run; the reached (>= 0) entries of row k
+ * sum to F[k].
+ * The bit-parallel solver stores the level of every newly visited (vertex, group) bit as its
+ * levels produce them (the edge-counting pass plus one store kernel per level); the per-group
+ * solvers gather their distance array after each group.
+ * _run_dist: dist_dev is device memory (K x ld int32). */
+int msbfs_solver_run_dist(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
+                          int64_t* F, void* dist_dev, int64_t ld, msbfs_stats* st, void* stream);
+/* _run_dist_host: the same contract into host memory. One solver pass of rows at a time is
+ * staged through a solver-owned device buffer (bit-parallel: 64 * words rows of n int32, not
+ * K rows) and pinned memory; if that buffer cannot be allocated the call fails with an error
+ * (msbfs_last_error). */
+int msbfs_solver_run_dist_host(msbfs_solver s, int64_t K, const int64_t* qoff,
+                               const int32_t* qids, int64_t* F, int32_t* dist_host, int64_t ld,
+                               msbfs_stats* st, void* stream);
 /* per-level records of the solver's last run / hybrid phase: copies min(n, cap) records to out
  * (nullable) and returns n (or -1 for a null solver) */
 int64_t msbfs_solver_levels(msbfs_solver s, msbfs_level* out, int64_t cap);

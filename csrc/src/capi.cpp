@@ -7,6 +7,7 @@
 #include <memory>
 
 #include "msbfs/device.hpp"
+#include "msbfs/dist_stage.hpp"
 #include "msbfs/graph.hpp"
 #include "msbfs/msbfs.h"
 
@@ -19,6 +20,9 @@ struct msbfs_solver_s {
   std::unique_ptr<msbfs::Solver> impl;
   int nthreads = 0;
   std::vector<msbfs::LevelRec> recs;  // per-level records of the last run / phase
+  // host-output distance runs: one solver pass of rows on the device, a pinned chunk on the host
+  msbfs::DevBuf dist_stage;
+  std::unique_ptr<msbfs::PinnedBuf> dist_pinned;
 };
 
 namespace {
@@ -47,6 +51,11 @@ T* dup(const std::vector<T>& v) {
 }
 
 hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+// msbfs_solver_run_dist_host: rows of a per-group solver's staging buffer (the bit-parallel
+// solver stages one pass), and the pinned chunk the rows come down through
+constexpr int64_t kDistStageBudget = int64_t{256} << 20;
+constexpr int64_t kDistPinnedBytes = int64_t{16} << 20;
 }  // namespace
 
 // run fn on the solver's device stream with event timing and fill st
@@ -428,6 +437,80 @@ int msbfs_solver_run(msbfs_solver s, int64_t K, const int64_t* qoff, const int32
     timed(s, stream, st, "solver run", [&](msbfs::RunStats* rs, hipStream_t hs) {
       s->impl->run(K, qoff, qids, F, edges2, rs, hs);
     });
+  });
+}
+
+namespace {
+void check_dist_args(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
+                     const int64_t* F, const void* dist, int64_t ld) {
+  if (!s || !s->impl) msbfs::fail("null solver");
+  if (K < 0 || (K > 0 && (!qoff || !F))) msbfs::fail("run_dist: bad query set");
+  if (K > 0 && qoff[K] > qoff[0] && !qids) msbfs::fail("run_dist: bad query set");
+  if (K > 0 && !dist) msbfs::fail("run_dist: no distance output");
+  if (ld < s->graph->g.n) msbfs::fail("run_dist: ld must be at least n");
+}
+}  // namespace
+
+int msbfs_solver_run_dist(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
+                          int64_t* F, void* dist_dev, int64_t ld, msbfs_stats* st, void* stream) {
+  return guard([&] {
+    check_dist_args(s, K, qoff, qids, F, dist_dev, ld);
+    timed(s, stream, st, "solver run_dist", [&](msbfs::RunStats* rs, hipStream_t hs) {
+      if (K > 0) s->impl->run_dist(K, qoff, qids, F, (int32_t*)dist_dev, ld, rs, hs);
+    });
+  });
+}
+
+int msbfs_solver_run_dist_host(msbfs_solver s, int64_t K, const int64_t* qoff,
+                               const int32_t* qids, int64_t* F, int32_t* dist_host, int64_t ld,
+                               msbfs_stats* st, void* stream) {
+  return guard([&] {
+    check_dist_args(s, K, qoff, qids, F, dist_host, ld);
+    const int64_t n = s->graph->g.n;
+    timed(s, stream, st, "solver run_dist_host", [&](msbfs::RunStats* rs, hipStream_t hs) {
+      if (K <= 0) return;
+      const int64_t rows = msbfs::dist_stage_rows(s->impl->pass_groups(), K, n, kDistStageBudget);
+      // (an allocation that fails throws; the guard turns it into an error return)
+      s->dist_stage.ensure((size_t)rows * std::max<int64_t>(n, 1) * sizeof(int32_t));
+      const int64_t chunk =
+          std::min<int64_t>(kDistPinnedBytes / (int64_t)sizeof(int32_t), std::max<int64_t>(rows * n, 1));
+      if (!s->dist_pinned || s->dist_pinned->bytes < (size_t)chunk * sizeof(int32_t))
+        s->dist_pinned = std::make_unique<msbfs::PinnedBuf>((size_t)chunk * sizeof(int32_t));
+      int32_t* dev = s->dist_stage.as<int32_t>();
+      int32_t* pin = s->dist_pinned->as<int32_t>();
+      for (int64_t k0 = 0; k0 < K; k0 += rows) {
+        const int64_t nb = std::min(rows, K - k0);
+        s->impl->run_dist(nb, qoff + k0, qids, F + k0, dev, n, rs, hs);
+        for (int64_t a = 0; a < nb * n; a += chunk) {
+          const int64_t b = std::min(a + chunk, nb * n);
+          MSBFS_HIP_CHECK(hipMemcpyAsync(pin, dev + a, (size_t)(b - a) * sizeof(int32_t),
+                                         hipMemcpyDeviceToHost, hs));
+          MSBFS_HIP_CHECK(hipStreamSynchronize(hs));
+          msbfs::dist_scatter_flat(pin, a, b, n, ld, dist_host + k0 * ld);
+        }
+      }
+    });
+  });
+}
+
+int msbfs_cpu_run_dist(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
+                       const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist,
+                       int64_t ld, int nthreads) {
+  return guard([&] {
+    if (n < 0 || K < 0 || (K > 0 && (!qoff || !F || !dist))) msbfs::fail("cpu_run_dist: bad arguments");
+    if (ld < n) msbfs::fail("cpu_run_dist: ld must be at least n");
+    if (K == 0) return;
+    msbfs::HostCsr g;
+    g.n = n;
+    g.rowptr.assign(rowptr, rowptr + n + 1);
+    g.col.assign(col, col + rowptr[n]);
+    g.m = rowptr[n] / 2;
+    msbfs::QuerySet q;
+    q.off.assign(qoff, qoff + K + 1);
+    q.ids.assign(qids, qids + qoff[K]);
+    std::vector<int64_t> f;
+    msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, dist, ld);
+    std::memcpy(F, f.data(), K * sizeof(int64_t));
   });
 }
 

@@ -45,7 +45,7 @@ int64_t cpu_msbfs_F(const HostCsr& g, const int32_t* src, int64_t nsrc, std::vec
 }
 
 void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
-                   std::vector<int64_t>* edges, int nthreads) {
+                   std::vector<int64_t>* edges, int nthreads, int32_t* dist_out, int64_t ld) {
   const int64_t K = q.K();
   F.assign(K, 0);
   if (edges) edges->assign(K, 0);
@@ -61,6 +61,8 @@ void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
       int64_t e = 0;
       F[k] = cpu_msbfs_F(g, q.ids.data() + q.off[k], q.off[k + 1] - q.off[k], dist, queue, &e);
       if (edges) (*edges)[k] = e;
+      // (the worker's distance array already is the row: -1 unreached, 0 the valid sources)
+      if (dist_out) std::copy(dist.begin(), dist.begin() + g.n, dist_out + k * ld);
     }
   };
   if (nthreads == 1) {

@@ -33,6 +33,7 @@
 //   bitpar/bits.hpp                      pure bit helpers (HIP-free, pinned by the host self-test)
 //   bitpar/common.hpp  init.hpp  push.hpp  hybrid.hpp  tiles.hpp      kernels by family; the pull
 //   bitpar/pull.hpp  pull_full.hpp  pull_lists.hpp  pull_tail.hpp     levels': pulls, lists, tail push
+//   bitpar/record.hpp                    the distance output of run_dist (per-level record kernels)
 //   bitpar_solver.hip  construction, batches, the level loop (direction choice, reductions)
 //   bitpar_push.hip    top-down levels and the device-driven level batches
 //   bitpar_pull.hip    bottom-up levels (prefix pull + tail push, narrow / lean / chunk pulls),
@@ -50,6 +51,7 @@
 
 #include "common.hpp"
 #include "pull_plan.hpp"
+#include "record.hpp"
 
 namespace msbfs {
 namespace bp {
@@ -80,6 +82,9 @@ class BitparSolver final : public Solver {
 
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
            RunStats* st, hipStream_t stream) override;
+  // run() plus dist_dev[k * ld + v] (bitpar/record.hpp); forces the edge-counting instantiation
+  void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
+                int64_t ld, RunStats* st, hipStream_t stream) override;
   void tune(const std::string& spec) override { tun_.parse(spec); }
   int64_t pass_groups() const override { return 64 * (int64_t)std::min(maxW_, opt.max_words); }
   // graph-derived tables and worst-case scratch, built before any timed run (bitpar_pull.hip)
@@ -440,6 +445,31 @@ class BitparSolver final : public Solver {
     return num_cus_;
   }
   DevBuf bctr_;  // (kBatch+1) Ctr slots, then (kBatch+1) x 16 alive words
+  // ---- distance output (bitpar/record.hpp)
+  Record rec_;     // set by run_dist for its duration; rec_.out == nullptr otherwise
+  DevBuf n2o_;     // inverse of g_.old2new, built on first use, cached per map
+  DevBuf rslot_;   // the dense walk's marks (record.hpp), n int32, zero between levels
+  const void* n2o_key_ = nullptr;
+  const int32_t* new2old(hipStream_t s);
+  // the level-0 zeros of a batch's source pairs / one level's new bits off the new frontier list
+  // fl_[fc ^ 1] (length from ctr; new bits = a, or a & ~b with DIFF), right after the level's
+  // k_count_frontier. Both launch nothing unless a distance run is under way.
+  void record_sources(const int32_t* pv, const int32_t* pk, int64_t np, hipStream_t s);
+  template <int W, bool DIFF>
+  void record_level(const int32_t* fl, const Ctr* ctr, const uint64_t* a, const uint64_t* b,
+                    int64_t nmax, int grid_cap, uint32_t level, hipStream_t s,
+                    bool may_dense = true) {
+    if (!rec_.out) return;
+    // (nmax bounds the list's length; the dense walk only where the list can be large)
+    const bool dense = may_dense && rec_.slot && nmax * kRecordDenseDiv >= g_.n;
+    if (dense)
+      k_record_mark<<<grid_for(nmax, kBlock, grid_cap), kBlock, 0, s>>>(fl, ctr, rec_.new2old,
+                                                                        g_.n, rec_.slot);
+    k_record_levels<W, DIFF><<<grid_for(dense ? g_.n : nmax, kBlock, grid_cap), kBlock, 0, s>>>(
+        fl, ctr, a, b, rec_.new2old, dense ? rec_.slot : nullptr, g_.n,
+        rec_.out + rec_.k0 * rec_.ld, rec_.ld, rec_.nb, (int32_t)level);
+    MSBFS_HIP_CHECK(hipGetLastError());
+  }
   std::unique_ptr<PinnedBuf> hbctr_;
 };
 

@@ -526,6 +526,8 @@ int BitparSolver::level_bu(Loop& S, hipStream_t s) {
         slabE<W>(L.rows));
     MSBFS_HIP_CHECK(hipGetLastError());
     L.rows += gc;
+    record_level<W, true>(fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(), L.O, L.R,
+                          S.nact + S.nactw, kMaxGrid, S.level, s);
   }
   std::swap(act_[0], act_[1]);
   std::swap(actw_[0], actw_[1]);

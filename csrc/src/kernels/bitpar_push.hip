@@ -75,6 +75,8 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
         nullptr, slabF<W>(rows), slabE<W>(rows));
     rows += gc;
     MSBFS_HIP_CHECK(hipGetLastError());
+    record_level<W, false>(fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(),
+                           acc_[S.ac ^ 1].as<uint64_t>(), nullptr, nt_max, grid, S.level, s);
   }
   S.ac ^= 1;
   S.fsrc_acc = true;
@@ -194,10 +196,15 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
                                S.fsrc_acc ? acc_[S.ac].as<uint64_t>() : nullptr,
                                anyvis_.as<uint32_t>(), slabF_.as<uint32_t>(), S.lazy ? 1 : 0,
                                &prev->act2.v);
-    if constexpr (!FUSE)
+    if constexpr (!FUSE) {
       k_count_frontier<W, COUNT, false><<<grid, kBlock, 0, s>>>(
           fl_[S.fc ^ 1].as<int32_t>(), cur, g_.rowptr, acc_[S.ac ^ 1].as<uint64_t>(), nullptr,
           slabF_.as<uint32_t>(), slabE_.as<unsigned long long>());
+      // (a level after the frontier died or the batch stopped left cur->fl2 = 0: no stores; the
+      // list's length is unknown here, and these graphs' frontiers are small: always the list)
+      record_level<W, false>(fl_[S.fc ^ 1].as<int32_t>(), cur, acc_[S.ac ^ 1].as<uint64_t>(),
+                             nullptr, n, grid, level, s, false);
+    }
     k_level_reduce<W, COUNT><<<W * rg, kBlock, 0, s>>>(slabF_.as<uint32_t>(),
                                                        slabE_.as<unsigned long long>(), grid, rg,
                                                        sm.F, sm.E, aslot + 16 * (i + 1), weight, BuGate{});

@@ -75,10 +75,93 @@ void BitparSolver::run(int64_t K, const int64_t* qoff, const int32_t* qids, int6
   if (st) st->builds += plen_builds_ - builds0;
 }
 
+// ---- distance output (bitpar/record.hpp) --------------------------------------------------------
+// new2old[old2new[v]] = v (old2new is a permutation of [0, n))
+static __global__ __launch_bounds__(kBlock) void k_invert_map(const int32_t* old2new, int64_t n,
+                                                              int32_t* new2old) {
+  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n;
+       v += (int64_t)gridDim.x * kBlock) {
+    const int32_t w = old2new[v];
+    if (w >= 0 && w < n) new2old[w] = (int32_t)v;
+  }
+}
+
+// Level 0: the batch's (source, local group) pairs, original ids, range-checked by start_batch.
+// Duplicates store the same zero twice. out: row 0 = the batch's first group.
+static __global__ __launch_bounds__(kBlock) void k_record_sources(const int32_t* pv,
+                                                                  const int32_t* pk, int64_t np,
+                                                                  int64_t n, int64_t nb,
+                                                                  int32_t* out, int64_t ld) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < np;
+       i += (int64_t)gridDim.x * kBlock) {
+    const int32_t v = pv[i], k = pk[i];
+    if (v >= 0 && v < n && k >= 0 && k < nb) out[(int64_t)k * ld + v] = 0;
+  }
+}
+
+const int32_t* BitparSolver::new2old(hipStream_t s) {
+  if (!g_.old2new) return nullptr;
+  if (n2o_key_ != (const void*)g_.old2new) {
+    n2o_.ensure((size_t)std::max<int64_t>(g_.n, 1) * sizeof(int32_t));
+    k_invert_map<<<grid_for(g_.n, kBlock, 2048), kBlock, 0, s>>>(g_.old2new, g_.n,
+                                                                 n2o_.as<int32_t>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+    n2o_key_ = g_.old2new;
+  }
+  return n2o_.as<int32_t>();
+}
+
+void BitparSolver::record_sources(const int32_t* pv, const int32_t* pk, int64_t np,
+                                  hipStream_t s) {
+  if (!rec_.out || np <= 0) return;
+  k_record_sources<<<grid_for(np, kBlock), kBlock, 0, s>>>(
+      pv, pk, np, g_.n, rec_.nb, rec_.out + rec_.k0 * rec_.ld, rec_.ld);
+  MSBFS_HIP_CHECK(hipGetLastError());
+}
+
+void BitparSolver::run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                            int32_t* dist_dev, int64_t ld, RunStats* st, hipStream_t stream) {
+  const int64_t n = g_.n;
+  if (!dist_dev) fail("run_dist: no distance output");
+  if (ld < n) fail("run_dist: ld must be at least n");
+  // (cleared however the run ends: a later run() must launch nothing of this)
+  struct Scope {
+    Record& r;
+    ~Scope() { r = Record{}; }
+  } scope{rec_};
+  rec_.out = dist_dev;
+  rec_.ld = ld;
+  rec_.new2old = new2old(stream);
+  if (rec_.new2old && n > 0) {
+    // (zeroed per run: a run that failed half way may have left marks)
+    rslot_.ensure((size_t)n * sizeof(int32_t));
+    MSBFS_HIP_CHECK(hipMemsetAsync(rslot_.p, 0, (size_t)n * sizeof(int32_t), stream));
+    rec_.slot = rslot_.as<int32_t>();
+  }
+  const int64_t builds0 = plen_builds_;
+  const int mw = std::min(maxW_, opt.max_words);
+  for (Batch b = batch_at(K, 0, mw); b.k0 < K; b = batch_at(K, b.k0 + b.nb, mw)) {
+    rec_.k0 = b.k0;
+    rec_.nb = b.nb;
+    // the -1 fill of the pass's rows, columns [0, n) only
+    if (n > 0) {
+      int32_t* rows = dist_dev + b.k0 * ld;
+      if (ld == n)
+        MSBFS_HIP_CHECK(hipMemsetAsync(rows, 0xFF, (size_t)b.nb * n * sizeof(int32_t), stream));
+      else
+        MSBFS_HIP_CHECK(hipMemset2DAsync(rows, (size_t)ld * sizeof(int32_t), 0xFF,
+                                         (size_t)n * sizeof(int32_t), (size_t)b.nb, stream));
+    }
+    run_batch(b.w, b.k0, b.nb, qoff, qids, F + b.k0, nullptr, st, stream);
+    if (st) st->batches++;
+  }
+  if (st) st->builds += plen_builds_ - builds0;
+}
+
 void BitparSolver::run_batch(int w, int64_t k0, int64_t nb, const int64_t* qoff,
                              const int32_t* qids, int64_t* F, int64_t* edges2, RunStats* st,
                              hipStream_t s) {
-  const bool c = edges2 != nullptr || opt.count_edges;
+  const bool c = edges2 != nullptr || opt.count_edges || rec_.out != nullptr;
 #define MSBFS_BP_CASE(WW)                                                   \
   case WW:                                                                  \
     if (c) batch_impl<WW, true>(k0, nb, qoff, qids, F, edges2, st, s);      \
@@ -159,6 +242,7 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
         acc_[S.ac].as<uint64_t>(), stamp_.as<int32_t>(), epoch_, fl_[S.fc].as<int32_t>(),
         ctr_.as<Ctr>(), sm.E, sm.alive[0], anyvis_.as<uint32_t>(), g_.old2new);
     MSBFS_HIP_CHECK(hipGetLastError());
+    if constexpr (COUNT) record_sources(dpv, dpk, np, s);  // (a distance run's level 0)
   }
   const HostCtr c = read_ctr(s);  // also retires the pinned/host source copies
   S.nf = c.fl2;

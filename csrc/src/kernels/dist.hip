@@ -336,6 +336,30 @@ __global__ __launch_bounds__(kBlock) void k_reduce_fsum(const int32_t* dist, con
   }
 }
 
+// Distance output (Solver::run_dist): one group's row, out[v] = dist[old2new ? old2new[v] : v]
+// for the user's ids v < n. Coalesced writes, a permutation gather on relabelled graphs; any
+// negative "unvisited" value comes out as -1.
+__global__ __launch_bounds__(kBlock) void k_gather_dist(const int32_t* dist,
+                                                        const int32_t* old2new, int64_t n,
+                                                        int32_t* out) {
+  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n;
+       v += (int64_t)gridDim.x * kBlock) {
+    int64_t i = old2new ? old2new[v] : v;
+    const int32_t d = (i >= 0 && i < n) ? dist[i] : -1;
+    out[v] = d < 0 ? -1 : d;
+  }
+}
+static void gather_dist(const DeviceGraph& g, const int32_t* dist, int32_t* out_row,
+                        hipStream_t s) {
+  if (g.n <= 0) return;
+  k_gather_dist<<<grid_for(g.n, kBlock, 4096), kBlock, 0, s>>>(dist, g.old2new, g.n, out_row);
+  MSBFS_HIP_CHECK(hipGetLastError());
+}
+static void check_dist_out(const DeviceGraph& g, const int32_t* dist_dev, int64_t ld) {
+  if (!dist_dev) fail("run_dist: no distance output");
+  if (ld < g.n) fail("run_dist: ld must be at least n");
+}
+
 // the first launch of a kernel of this unit loads its code object (1.5-2.8 ms, see
 // bp::load_code_objects): prepare() does it before any timed run
 static __global__ void k_load_dist() {}
@@ -368,6 +392,19 @@ class DistSolver final : public Solver {
 
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
            RunStats* st, hipStream_t s) override {
+    run_impl(K, qoff, qids, F, edges2, nullptr, 0, st, s);
+  }
+  void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
+                int64_t ld, RunStats* st, hipStream_t s) override {
+    check_dist_out(g_, dist_dev, ld);
+    run_impl(K, qoff, qids, F, nullptr, dist_dev, ld, st, s);
+  }
+
+ private:
+  // dout != nullptr: row k of it gets group k's distances (gathered before the next group's
+  // lazy reset scatters -1 over them)
+  void run_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
+                int32_t* dout, int64_t ld, RunStats* st, hipStream_t s) {
     const int64_t n = g_.n;
     int64_t maxs = 1;
     for (int64_t k = 0; k < K; ++k) maxs = std::max(maxs, qoff[k + 1] - qoff[k]);
@@ -501,13 +538,13 @@ class DistSolver final : public Solver {
         ++L;
         if (st) st->levels++;
       }
+      if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
       visited_ = lo + nf;  // every visited vertex sits in ord[0, lo + nf)
       F[k] = Fk;
       if (edges2) edges2[k] = E2;
     }
   }
 
- private:
   HostCtr read(hipStream_t s) {
     MSBFS_HIP_CHECK(hipMemcpyAsync(hctr_->p, ctr_.p, sizeof(Ctr), hipMemcpyDeviceToHost, s));
     MSBFS_HIP_CHECK(hipStreamSynchronize(s));
@@ -534,6 +571,17 @@ class SweepSolver final : public Solver {
   }
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
            RunStats* st, hipStream_t s) override {
+    run_impl(K, qoff, qids, F, edges2, nullptr, 0, st, s);
+  }
+  void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
+                int64_t ld, RunStats* st, hipStream_t s) override {
+    check_dist_out(g_, dist_dev, ld);
+    run_impl(K, qoff, qids, F, nullptr, dist_dev, ld, st, s);
+  }
+
+ private:
+  void run_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
+                int32_t* dout, int64_t ld, RunStats* st, hipStream_t s) {
     const int64_t n = g_.n;
     int64_t maxs = 1;
     for (int64_t k = 0; k < K; ++k) maxs = std::max(maxs, qoff[k + 1] - qoff[k]);
@@ -574,10 +622,10 @@ class SweepSolver final : public Solver {
       MSBFS_HIP_CHECK(hipStreamSynchronize(s));
       F[k] = (int64_t)h[0];
       if (edges2) edges2[k] = (int64_t)h[1];
+      if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
     }
   }
 
- private:
   const DeviceGraph& g_;
   DevBuf dist_, fl_, ctr_, red_, src_;
   std::unique_ptr<PinnedBuf> hctr_;

@@ -18,6 +18,7 @@
 #include "../cli/thread_group.hpp"
 #include "../src/kernels/bitpar/bits.hpp"
 #include "../src/kernels/bitpar/pull_plan.hpp"
+#include "msbfs/dist_stage.hpp"
 #include "msbfs/graph.hpp"
 
 using namespace msbfs;
@@ -465,6 +466,39 @@ static void bit_counter_cases() {
 }
 }  // namespace bits_test
 
+// the pass / row arithmetic of the host-output distance runs (msbfs/dist_stage.hpp)
+static void dist_stage_cases() {
+  // bit-parallel: one pass of rows, never more than K; no budget applies
+  CHECK(dist_stage_rows(1024, 5000, 1 << 20, 1 << 20) == 1024);
+  CHECK(dist_stage_rows(128, 100, 1 << 20, 1) == 100);
+  CHECK(dist_stage_rows(64, 0, 10, 1 << 20) == 0);
+  // per-group solvers: any number of groups per call, rows bounded by the budget, at least one
+  CHECK(dist_stage_rows(INT64_MAX, 9, 1000, 4000 * 4) == 4);
+  CHECK(dist_stage_rows(INT64_MAX, 3, 1000, 4000 * 4) == 3);
+  CHECK(dist_stage_rows(INT64_MAX, 9, 1000, 10) == 1);
+  CHECK(dist_stage_rows(INT64_MAX, 9, 0, 10) == 2);  // (n = 0 counts as one element)
+  // flat chunks of a 3 x 5 matrix into rows 8 apart: every chunking gives the same rows and
+  // leaves the padding alone
+  const int64_t n = 5, ld = 8, rows = 3;
+  std::vector<int32_t> src(rows * n);
+  for (int64_t i = 0; i < rows * n; ++i) src[i] = (int32_t)(100 + i);
+  for (int64_t chunk : {1, 2, 4, 5, 7, 15, 40}) {
+    std::vector<int32_t> dst(rows * ld, -7);
+    for (int64_t a = 0; a < rows * n; a += chunk) {
+      const int64_t b = std::min(a + chunk, rows * n);
+      dist_scatter_flat(src.data() + a, a, b, n, ld, dst.data());
+    }
+    bool ok = true;
+    for (int64_t r = 0; r < rows; ++r)
+      for (int64_t c = 0; c < ld; ++c) ok &= dst[r * ld + c] == (c < n ? 100 + r * n + c : -7);
+    CHECK(ok);
+  }
+  std::vector<int32_t> none(4, -7);
+  dist_scatter_flat(src.data(), 0, 0, n, ld, none.data());
+  dist_scatter_flat(src.data(), 0, 3, 0, ld, none.data());  // (n = 0: nothing to place)
+  CHECK(none == std::vector<int32_t>(4, -7));
+}
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp";
   const std::string gp = dir + "/selftest_g.bin", qp = dir + "/selftest_q.bin";
@@ -475,6 +509,7 @@ int main(int argc, char** argv) {
   plan_test::tuning();
   bits_test::new_bits_cases();
   bits_test::bit_counter_cases();
+  dist_stage_cases();
   // generators: threaded == serial
   EdgeList e1 = gen_rmat(12, 8, 5, 0.57, 0.19, 0.19, true, 1);
   EdgeList e8 = gen_rmat(12, 8, 5, 0.57, 0.19, 0.19, true, T);
@@ -504,6 +539,23 @@ int main(int argc, char** argv) {
   cpu_msbfs_all(l1, q, F8, &E8, T);
   CHECK(F1 == F8 && E1 == E8);
   CHECK(argmin_first(F1) >= 0);
+  // ... and its distance rows: threaded == serial, padding untouched, each row sums to its F
+  {
+    const int64_t ld = l1.n + 3, K = q.K();
+    std::vector<int32_t> d1((size_t)(K * ld), 77), d8((size_t)(K * ld), 77);
+    std::vector<int64_t> Fd1, Fd8;
+    cpu_msbfs_all(l1, q, Fd1, nullptr, 1, d1.data(), ld);
+    cpu_msbfs_all(l1, q, Fd8, nullptr, T, d8.data(), ld);
+    CHECK(Fd1 == F1 && Fd8 == F1 && d1 == d8);
+    bool ok = true;
+    for (int64_t k = 0; k < K; ++k) {
+      int64_t sum = 0;
+      for (int64_t v = 0; v < l1.n; ++v) sum += std::max(d1[k * ld + v], 0);
+      ok &= sum == F1[k];
+      for (int64_t v = l1.n; v < ld; ++v) ok &= d1[k * ld + v] == 77;
+    }
+    CHECK(ok);
+  }
   unlink(gp.c_str());
   unlink((gp + ".csr").c_str());
   unlink(qp.c_str());

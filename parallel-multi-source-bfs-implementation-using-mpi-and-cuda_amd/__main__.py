@@ -20,6 +20,7 @@ def main(argv=None) -> int:
     from .engine import Engine, JobConfig
     cfg = JobConfig()
     json_out = False
+    dist_out = None  # --dist-out FILE: the winning group's distance row (n x int32 LE)
     i = 1
     while i < len(argv):
         a = argv[i]
@@ -45,6 +46,8 @@ def main(argv=None) -> int:
         elif a == "--json":
             json_out = True
             cfg.count_edges = True
+        elif a == "--dist-out" and has:
+            dist_out = argv[i + 1]; i += 1
         i += 1
     if cfg.num_gpu <= 0:
         print("msbfs: -gn must be >= 1", file=sys.stderr)
@@ -69,6 +72,10 @@ def main(argv=None) -> int:
                               "backend": ctx.backend, "traversed_edges": r.traversed_edges,
                               "F": [int(x) for x in r.F]}))
         sys.stdout.flush()
+        if dist_out is not None:  # after the report, outside the computation time
+            row = eng.winner_distances(r)
+            if row is not None:
+                row.astype("<i4").tofile(dist_out)
     eng.close()
     D.shutdown(ctx)
     return 0

@@ -167,6 +167,24 @@ class Engine:
             edges = int(D.allreduce_sum_i64(np.array([int(res.edges.sum())], np.int64), ctx)[0])
         return JobResult(min_k, min_f, self.preprocessing_time, dt, F, edges, res.stats)
 
+    def winner_distances(self, r: JobResult) -> Optional[np.ndarray]:
+        """The winning group's distance row (int32[n], original vertex ids, -1 unreached), or
+        None when there is no winner (K = 0). Outside the computation boundary: the per-group
+        distance solver for one group on device algorithms, the CPU path for --algo cpu."""
+        if self.queries.K == 0 or r.min_k < 0:
+            return None
+        q = self.queries.subset(np.array([r.min_k], np.int64))
+        if self.on_gpu:
+            with Solver(self.dgraph, "dist", max_groups=1) as s:
+                res = s.distances(q)
+        else:
+            g = self.graph_host if self.graph_host is not None else self.dgraph.download()
+            res = cpu_bfs(g, q, distances=True)
+        if int(res.F[0]) != int(r.min_f):
+            raise RuntimeError(f"the winner's distance row sums to {int(res.F[0])}, not to its "
+                               f"F {int(r.min_f)}")
+        return res.dist[0]
+
     def report(self, r: JobResult) -> str:
         return format_report(self.cfg.graph or self.cfg.gen or "", self.cfg.query or self.cfg.qgen or "",
                              r.min_k, r.min_f, self.cfg.num_gpu, r.preprocessing_time,

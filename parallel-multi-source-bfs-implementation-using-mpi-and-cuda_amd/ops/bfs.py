@@ -29,6 +29,25 @@ class BfsResult:
     F: np.ndarray                      # int64[K]
     edges: Optional[np.ndarray] = None  # int64[K], Graph500 traversed edges per group (if asked)
     stats: dict = field(default_factory=dict)
+    # int32[K, n] per-vertex distances (original vertex ids; -1 unreached) of a distances() /
+    # distances=True call; None otherwise, and when they went to a device buffer (out_ptr)
+    dist: Optional[np.ndarray] = None
+
+
+def _host_dist_out(K: int, n: int, out: Optional[np.ndarray], ld: Optional[int]):
+    """The host matrix a distance call writes and its row stride: `out` (C-contiguous int32
+    [K, >= n], written in place, columns >= n untouched) or a fresh [K, ld or n] array."""
+    if out is None:
+        ld = n if ld is None else int(ld)
+        if ld < n:
+            raise ValueError("ld must be at least n")
+        return np.full((K, ld), -1, dtype=np.int32), ld
+    if (out.dtype != np.int32 or out.ndim != 2 or not out.flags.c_contiguous
+            or out.shape[0] != K or out.shape[1] < n):
+        raise ValueError("out must be a C-contiguous int32 array of shape [K, >= n]")
+    if ld is not None and int(ld) != out.shape[1]:
+        raise ValueError("ld must equal out.shape[1]")
+    return out, out.shape[1]
 
 
 class Solver:
@@ -88,6 +107,42 @@ class Solver:
                 native.ptr(F, C.c_int64), native.ptr(E, C.c_int64) if E is not None else None,
                 C.byref(st), C.c_void_p(stream) if stream else None))
         return BfsResult(F, None if E is None else E // 2, st.as_dict())
+
+    def distances(self, queries: QuerySet, out_ptr: Optional[int] = None,
+                  ld: Optional[int] = None, stream: Optional[int] = None,
+                  out: Optional[np.ndarray] = None) -> BfsResult:
+        """F plus the per-vertex distances of every group: dist[k, v] = BFS level of vertex v
+        (original ids, also on relabelled graphs) from group k, 0 for its valid sources, -1 where
+        unreached; dist[k][dist[k] >= 0].sum() == F[k].
+
+        Host output (default): BfsResult.dist is int32[K, n] (a view of the first n columns of
+        `out` when given: a C-contiguous int32 [K, ld >= n] array written in place, its columns
+        >= n untouched). One solver pass of rows at a time is staged on the device.
+        out_ptr: an integer device address of K x ld int32 (ld defaults to n) that receives the
+        rows instead; nothing is copied to the host and BfsResult.dist is None."""
+        K = queries.K
+        n = self.graph.n
+        F = np.zeros(K, dtype=np.int64)
+        st = native.Stats()
+        L = native.lib()
+        sp = C.c_void_p(stream) if stream else None
+        qo, qi = native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32)
+        if out_ptr is not None:
+            if out is not None:
+                raise ValueError("give out_ptr (device) or out (host), not both")
+            ld = n if ld is None else int(ld)
+            if ld < n:
+                raise ValueError("ld must be at least n")
+            if K:
+                native.check(L.msbfs_solver_run_dist(self._h, K, qo, qi, native.ptr(F, C.c_int64),
+                                                     C.c_void_p(int(out_ptr)), ld, C.byref(st), sp))
+            return BfsResult(F, None, st.as_dict(), None)
+        D, ld = _host_dist_out(K, n, out, ld)
+        if K:
+            native.check(L.msbfs_solver_run_dist_host(self._h, K, qo, qi, native.ptr(F, C.c_int64),
+                                                      native.ptr(D, C.c_int32), ld, C.byref(st),
+                                                      sp))
+        return BfsResult(F, None, st.as_dict(), D[:, :n])
 
     def level_trace(self) -> list:
         """Per-level records of the last run / hybrid phase (bit-parallel solver): batch, level,
@@ -213,12 +268,24 @@ class Solver:
         self.close()
 
 
-def cpu_bfs(graph: Graph, queries: QuerySet, threads: int = 0, count_edges: bool = False
-            ) -> BfsResult:
-    """Query-parallel host BFS (native C++ threads)."""
+def cpu_bfs(graph: Graph, queries: QuerySet, threads: int = 0, count_edges: bool = False,
+            distances: bool = False, out: Optional[np.ndarray] = None) -> BfsResult:
+    """Query-parallel host BFS (native C++ threads). distances=True: BfsResult.dist is the
+    int32[K, n] distance matrix (see Solver.distances; `out` as there)."""
     K = queries.K
     F = np.zeros(K, dtype=np.int64)
     E = np.zeros(K, dtype=np.int64) if count_edges else None
+    if distances:
+        D, ld = _host_dist_out(K, graph.n, out, None)
+        if K:
+            native.check(native.lib().msbfs_cpu_run_dist(
+                graph.n, native.ptr(graph.rowptr, C.c_int64), native.ptr(graph.col, C.c_int32), K,
+                native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32),
+                native.ptr(F, C.c_int64), native.ptr(D, C.c_int32), ld, int(threads)))
+        if E is not None and K:
+            deg = np.diff(graph.rowptr)
+            E[:] = [int(deg[D[k, :graph.n] >= 0].sum()) // 2 for k in range(K)]
+        return BfsResult(F, E, {}, D[:, :graph.n])
     if K:
         native.check(native.lib().msbfs_cpu_run(
             graph.n, native.ptr(graph.rowptr, C.c_int64), native.ptr(graph.col, C.c_int32), K,
@@ -229,15 +296,23 @@ def cpu_bfs(graph: Graph, queries: QuerySet, threads: int = 0, count_edges: bool
 
 
 def multi_source_bfs(graph: Union[Graph, DeviceGraph], queries: QuerySet, algo: str = "auto",
-                     device: int = 0, count_edges: bool = False, **opts) -> BfsResult:
-    """One-shot convenience wrapper (creates and frees a Solver)."""
+                     device: int = 0, count_edges: bool = False, distances: bool = False,
+                     **opts) -> BfsResult:
+    """One-shot convenience wrapper (creates and frees a Solver). distances=True: the result
+    also carries the int32[K, n] distance matrix (Solver.distances); the traversed-edge counts
+    then come from a second, plain run when count_edges is set too."""
     if algo == "cpu":
         if isinstance(graph, DeviceGraph):
             graph = graph.download()
-        return cpu_bfs(graph, queries, count_edges=count_edges)
+        return cpu_bfs(graph, queries, count_edges=count_edges, distances=distances)
     dg = graph if isinstance(graph, DeviceGraph) else DeviceGraph.from_host(graph, device)
     with Solver(dg, algo, max_groups=max(1, queries.K), **opts) as s:
-        return s.run(queries, count_edges=count_edges)
+        if not distances:
+            return s.run(queries, count_edges=count_edges)
+        r = s.distances(queries)
+        if count_edges:
+            r.edges = s.run(queries, count_edges=True).edges
+        return r
 
 
 def argmin_first(F: np.ndarray) -> int:

@@ -109,6 +109,12 @@ def _sig(lib):
         "msbfs_solver_prepare_hybrid": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "msbfs_solver_prepare_queries": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
         "msbfs_solver_run": (C.c_int, [vp, C.c_int64, i64p, i32p, i64p, i64p, P(Stats), vp]),
+        "msbfs_solver_run_dist": (C.c_int, [vp, C.c_int64, i64p, i32p, i64p, vp, C.c_int64,
+                                            P(Stats), vp]),
+        "msbfs_solver_run_dist_host": (C.c_int, [vp, C.c_int64, i64p, i32p, i64p, i32p, C.c_int64,
+                                                 P(Stats), vp]),
+        "msbfs_cpu_run_dist": (C.c_int, [C.c_int64, i64p, i32p, C.c_int64, i64p, i32p, i64p, i32p,
+                                         C.c_int64, C.c_int]),
         "msbfs_solver_free": (None, [vp]),
         "msbfs_solver_levels": (C.c_int64, [vp, P(Level), C.c_int64]),
         "msbfs_argmin": (C.c_int64, [i64p, C.c_int64]),
