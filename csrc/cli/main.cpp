@@ -14,6 +14,9 @@
 //   --no-cache is accepted)  --json  --sort-rows  --no-relabel  --repeat R
 //   --dist-out FILE  after the report, rank 0 writes the winning group's distance row (n x int32
 //              little endian, original vertex ids, -1 unreached); nothing when K = 0
+//   --parent-out FILE  likewise the winning group's BFS parent row (n x int32: a source is its own
+//              parent, -1 unreached, else the first neighbour one level nearer in the row order
+//              of the graph the run used); may be given together with --dist-out
 //   --spmd N   (N >= 1) single-process multi-GPU: N ranks as N threads of this process (thread r on device
 //              r % -gn), RCCL communicators from ncclCommInitAll when every rank owns a GPU
 //   --dist {auto,roundrobin,hybrid,hybrid-coded}  multi-rank decomposition (auto: hybrid when > 1
@@ -56,6 +59,7 @@ struct Args {
   bool cache = false, json = false, sort_rows = false, relabel = true;
   bool host_csr = false;  // build the CSR of a graph file on the host (default: on the device)
   std::string dist_out;   // --dist-out FILE: the winning group's distance row (n x int32 LE)
+  std::string parent_out;  // --parent-out FILE: the winning group's parent row (n x int32 LE)
 };
 
 std::vector<std::string> split(const std::string& s, char d) {
@@ -618,8 +622,11 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
     // --dist-out: after the report (outside the computation boundary) rank 0 computes the
     // winning group's distance row, with the per-group distance solver for one group (CPU path
     // for --algo cpu), and writes n little-endian int32 (original vertex ids, -1 unreached)
-    if (!a.dist_out.empty() && comm->rank() == 0 && K > 0 && minK >= 0) {
+    // --parent-out: the same run also gives the winner's parent row (run_parents)
+    const bool want_parent = !a.parent_out.empty();
+    if ((!a.dist_out.empty() || want_parent) && comm->rank() == 0 && K > 0 && minK >= 0) {
       std::vector<int32_t> row((size_t)std::max<int64_t>(nverts, 1), -1);
+      std::vector<int32_t> prow(want_parent ? row.size() : 0, -1);
       const int64_t woff[2] = {0, q.off[minK + 1] - q.off[minK]};
       const int32_t* wids = q.ids.data() + q.off[minK];
       int64_t Fw = 0;
@@ -628,22 +635,37 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
         w.off.assign(woff, woff + 2);
         w.ids.assign(wids, wids + woff[1]);
         std::vector<int64_t> f;
-        cpu_msbfs_all(hg, w, f, nullptr, 1, row.data(), nverts);
+        cpu_msbfs_all(hg, w, f, nullptr, 1, row.data(), nverts,
+                      want_parent ? prow.data() : nullptr);
         Fw = f[0];
       } else {
         std::unique_ptr<Solver> ds = make_dist_solver(dg);
-        DevBuf drow((size_t)std::max<int64_t>(nverts, 1) * sizeof(int32_t));
-        ds->run_dist(1, woff, wids, &Fw, drow.as<int32_t>(), nverts, nullptr, stream);
+        const size_t rb = (size_t)std::max<int64_t>(nverts, 1) * sizeof(int32_t);
+        DevBuf drow(rb), dprow(want_parent ? rb : 0);
+        if (want_parent)
+          ds->run_parents(1, woff, wids, &Fw, drow.as<int32_t>(), dprow.as<int32_t>(), nverts,
+                          nullptr, stream);
+        else
+          ds->run_dist(1, woff, wids, &Fw, drow.as<int32_t>(), nverts, nullptr, stream);
         MSBFS_HIP_CHECK(hipMemcpyAsync(row.data(), drow.p, (size_t)nverts * sizeof(int32_t),
                                        hipMemcpyDeviceToHost, stream));
+        if (want_parent)
+          MSBFS_HIP_CHECK(hipMemcpyAsync(prow.data(), dprow.p, (size_t)nverts * sizeof(int32_t),
+                                         hipMemcpyDeviceToHost, stream));
         MSBFS_HIP_CHECK(hipStreamSynchronize(stream));
       }
-      if (Fw != minF) fail("--dist-out: the winner's distance row sums to " + std::to_string(Fw) +
-                           ", not to its F " + std::to_string(minF));
-      FILE* f = fopen(a.dist_out.c_str(), "wb");
-      if (!f) fail("--dist-out: could not open " + a.dist_out);
-      const size_t wr = fwrite(row.data(), sizeof(int32_t), (size_t)nverts, f);
-      if (fclose(f) != 0 || wr != (size_t)nverts) fail("--dist-out: short write to " + a.dist_out);
+      if (Fw != minF)
+        fail(std::string(a.dist_out.empty() ? "--parent-out" : "--dist-out") +
+             ": the winner's distance row sums to " + std::to_string(Fw) + ", not to its F " +
+             std::to_string(minF));
+      auto write_row = [&](const std::string& path, const std::vector<int32_t>& r, const char* flag) {
+        FILE* f = fopen(path.c_str(), "wb");
+        if (!f) fail(std::string(flag) + ": could not open " + path);
+        const size_t wr = fwrite(r.data(), sizeof(int32_t), (size_t)nverts, f);
+        if (fclose(f) != 0 || wr != (size_t)nverts) fail(std::string(flag) + ": short write to " + path);
+      };
+      if (!a.dist_out.empty()) write_row(a.dist_out, row, "--dist-out");
+      if (want_parent) write_row(a.parent_out, prow, "--parent-out");
     }
     comm.reset();
   } catch (const std::exception& e) {
@@ -691,6 +713,7 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--no-relabel")) a.relabel = false;
     else if (!strcmp(argv[i], "--host-csr")) a.host_csr = true;
     else if (!strcmp(argv[i], "--dist-out") && has) a.dist_out = argv[++i];
+    else if (!strcmp(argv[i], "--parent-out") && has) a.parent_out = argv[++i];
   }
   int rc = 0;
   if (a.spmd >= 1) {

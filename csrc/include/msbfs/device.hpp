@@ -124,8 +124,21 @@ void device_graph_sort_rows(DeviceGraph& g, hipStream_t s);
 // the graph alone: ranks with the same setting number vertices alike.
 void device_graph_relabel_by_degree(DeviceGraph& g, hipStream_t s);
 
+// The inverse of a graph's relabel map (new2old[old2new[v]] = v) in device memory, built on first
+// use and kept until the graph gets another map; nullptr for a graph that keeps its ids. Solvers
+// that write results by user id (distance and parent output) hold one. (kernels/gen.hip)
+struct InverseMap {
+  DevBuf buf;
+  const void* key = nullptr;
+  const int32_t* get(const DeviceGraph& g, hipStream_t s);
+};
+
 // ---- solvers ---------------------------------------------------------------------------------
 constexpr int kDefaultWideDegree = 32;
+// Parent output (Solver::run_parents): rows of at least this many entries are searched by more
+// than one lane group (bit-parallel: a block per vertex, per-group solvers: a wave). A constant,
+// not a tuning key: the result does not depend on it. msbfs_parents_wide_degree() returns it.
+constexpr int kParentsWideDegree = 256;
 struct SolverOptions {
   double alpha = 14.0;  // top-down -> bottom-up when frontier edges > unexplored edges / alpha
   double beta = 24.0;   // bottom-up -> top-down when frontier vertices < active vertices / beta
@@ -153,6 +166,17 @@ class Solver {
                         int32_t* dist_dev, int64_t ld, RunStats* st, hipStream_t stream) {
     (void)K, (void)qoff, (void)qids, (void)F, (void)dist_dev, (void)ld, (void)st, (void)stream;
     fail("distance output is not supported by this solver");
+  }
+  // run_dist() plus the BFS parents: parent_dev[k * ld + v] (laid out and padded like dist_dev)
+  // = v for the valid sources of group k, -1 where unreached, otherwise the user's id of the
+  // first neighbour u, in the order of v's row in the device graph (internal ids), with
+  // dist[k][u] == dist[k][v] - 1. Every solver on one DeviceGraph returns the same matrix.
+  virtual void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                           int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
+                           hipStream_t stream) {
+    (void)K, (void)qoff, (void)qids, (void)F, (void)dist_dev, (void)parent_dev, (void)ld,
+        (void)st, (void)stream;
+    fail("parent output is not supported by this solver");
   }
   // Groups one solver pass handles at once (bit-parallel: 64*W; per-group solvers run any
   // number in one call). Callers that overlap work between passes split runs at this size.

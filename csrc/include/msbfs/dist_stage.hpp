@@ -36,4 +36,18 @@ inline void dist_scatter_flat(const int32_t* chunk, int64_t a, int64_t b, int64_
   }
 }
 
+// One staged pass of a host-output run: the dense nb x n matrix on the device comes down in
+// pieces of at most `chunk` elements and goes into dst (row 0 = the pass's first row, rows ld
+// elements apart). copy(a, b) must leave elements [a, b) of the device matrix in pin[0, b - a)
+// before it returns (a device-to-host copy and its wait); nothing here touches the device.
+template <class Copy>
+inline void dist_stage_download(Copy&& copy, int64_t nb, int64_t n, int64_t chunk, int64_t ld,
+                                const int32_t* pin, int32_t* dst) {
+  for (int64_t a = 0; a < nb * n; a += chunk) {
+    const int64_t b = std::min(a + chunk, nb * n);
+    copy(a, b);
+    dist_scatter_flat(pin, a, b, n, ld, dst);
+  }
+}
+
 }  // namespace msbfs

@@ -94,11 +94,16 @@ QuerySet gen_queries(int64_t n, int64_t K, int64_t size, uint64_t seed);
 int64_t cpu_msbfs_F(const HostCsr& g, const int32_t* src, int64_t nsrc, std::vector<int32_t>& dist,
                     std::vector<int64_t>& queue, int64_t* edges = nullptr,
                     int32_t* levels = nullptr);
+// The BFS parents of one group from its distance array (as cpu_msbfs_F leaves it): parent[v] = v
+// where dist[v] == 0, -1 where unreached, else the first entry u of v's row with dist[u] ==
+// dist[v] - 1 (the row order decides, not which vertex discovered v). Writes parent[0, n).
+void cpu_parent_row(const HostCsr& g, const int32_t* dist, int32_t* parent);
 // All groups, query-parallel over nthreads host threads. dist_out != nullptr: row k of it (ld >= n
 // elements apart) gets group k's distances, -1 for unreached vertices; columns [n, ld) stay.
+// parent_out != nullptr: row k of it (same stride) gets group k's parents (cpu_parent_row).
 void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
                    std::vector<int64_t>* edges, int nthreads, int32_t* dist_out = nullptr,
-                   int64_t ld = 0);
+                   int64_t ld = 0, int32_t* parent_out = nullptr);
 
 // Reference tie-break (main.cu:381-397): first valid F, then strict '<'; returns -1 if K==0.
 int64_t argmin_first(const std::vector<int64_t>& F);

@@ -92,6 +92,13 @@ int msbfs_cpu_run_dist(int64_t n, const int64_t* rowptr, const int32_t* col, int
                        const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist,
                        int64_t ld, int nthreads);
 
+/* The same plus the BFS parents (see msbfs_solver_run_parents): parent[k*ld + v] (laid out and
+ * padded like dist) = v for the valid sources of group k, -1 where unreached, otherwise the first
+ * neighbour u in v's row of THIS host CSR with dist[k][u] == dist[k][v] - 1. */
+int msbfs_cpu_run_parents(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
+                          const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist,
+                          int32_t* parent, int64_t ld, int nthreads);
+
 /* ---- device graphs ---- */
 int msbfs_graph_from_host_csr(int device, int64_t n, const int64_t* rowptr, const int32_t* col,
                               msbfs_graph* out);
@@ -160,6 +167,38 @@ int msbfs_solver_run_dist(msbfs_solver s, int64_t K, const int64_t* qoff, const 
 int msbfs_solver_run_dist_host(msbfs_solver s, int64_t K, const int64_t* qoff,
                                const int32_t* qids, int64_t* F, int32_t* dist_host, int64_t ld,
                                msbfs_stats* st, void* stream);
+/* BFS parents (shortest paths to the set) next to the distances, from every solver. F and dist
+ * are returned exactly as by msbfs_solver_run_dist; parent[k*ld + v] is int32 in the ORIGINAL
+ * vertex ids, with the layout and padding rules of dist (the call writes columns [0, n) of
+ * every row, the -1 fill included, and never touches columns [n, ld)):
+ *   dist[k][v] == 0 (a valid source of group k)  parent[k][v] = v
+ *   dist[k][v] == -1                             parent[k][v] = -1
+ *   dist[k][v] == L > 0                          parent[k][v] = the first neighbour u of v with
+ *                                                dist[k][u] == L - 1
+ * "First" is the order of v's row in the solver's device graph: the CSR msbfs_graph_download
+ * returns (internal ids), mapped back through the relabel map. The result is therefore
+ * deterministic, identical across all device solvers on one graph handle, and checkable exactly
+ * from the download plus msbfs_graph_relabel_map; on a degree-relabelled graph (rows sorted,
+ * hubs first) every path takes the highest-degree parent available. Following parent[k] from v
+ * reaches, in dist[k][v] hops, the member of group k that v is nearest to.
+ * The bit-parallel solver searches the parents per level, 64 * words groups at once, against
+ * its own record of the bits seen through the previous level: per level a search kernel, one
+ * for the queued vertices of degree >= msbfs_parents_wide_degree() and a commit kernel, on top
+ * of a distance run. The per-group solvers scan each reached vertex's row in their distance
+ * array after each group.
+ * _run_parents: dist_dev and parent_dev are device memory (K x ld int32 each), both required. */
+int msbfs_solver_run_parents(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
+                             int64_t* F, void* dist_dev, void* parent_dev, int64_t ld,
+                             msbfs_stats* st, void* stream);
+/* _run_parents_host: the same contract into host memory, one solver pass of rows per matrix
+ * staged like msbfs_solver_run_dist_host (the per-group solvers give each matrix half of the
+ * staging budget); fails with an error if a staging buffer cannot be allocated. */
+int msbfs_solver_run_parents_host(msbfs_solver s, int64_t K, const int64_t* qoff,
+                                  const int32_t* qids, int64_t* F, int32_t* dist_host,
+                                  int32_t* parent_host, int64_t ld, msbfs_stats* st, void* stream);
+/* The degree from which the parent searches give a row to more than one lane group (a
+ * constant of the build; the results do not depend on it). */
+int msbfs_parents_wide_degree(void);
 /* per-level records of the solver's last run / hybrid phase: copies min(n, cap) records to out
  * (nullable) and returns n (or -1 for a null solver) */
 int64_t msbfs_solver_levels(msbfs_solver s, msbfs_level* out, int64_t cap);

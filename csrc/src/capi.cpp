@@ -23,6 +23,7 @@ struct msbfs_solver_s {
   // host-output distance runs: one solver pass of rows on the device, a pinned chunk on the host
   msbfs::DevBuf dist_stage;
   std::unique_ptr<msbfs::PinnedBuf> dist_pinned;
+  msbfs::DevBuf parent_stage;  // (host-output parents runs: the second matrix's rows)
 };
 
 namespace {
@@ -441,6 +442,19 @@ int msbfs_solver_run(msbfs_solver s, int64_t K, const int64_t* qoff, const int32
 }
 
 namespace {
+// the copy step of dist_stage_download: elements [a, b) of a staged device matrix into the
+// pinned chunk, waited for
+struct pinned_copy {
+  const int32_t* dev;
+  int32_t* pin;
+  hipStream_t hs;
+  pinned_copy(const int32_t* d, int32_t* p, hipStream_t s) : dev(d), pin(p), hs(s) {}
+  void operator()(int64_t a, int64_t b) const {
+    MSBFS_HIP_CHECK(hipMemcpyAsync(pin, dev + a, (size_t)(b - a) * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, hs));
+    MSBFS_HIP_CHECK(hipStreamSynchronize(hs));
+  }
+};
 void check_dist_args(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
                      const int64_t* F, const void* dist, int64_t ld) {
   if (!s || !s->impl) msbfs::fail("null solver");
@@ -481,13 +495,8 @@ int msbfs_solver_run_dist_host(msbfs_solver s, int64_t K, const int64_t* qoff,
       for (int64_t k0 = 0; k0 < K; k0 += rows) {
         const int64_t nb = std::min(rows, K - k0);
         s->impl->run_dist(nb, qoff + k0, qids, F + k0, dev, n, rs, hs);
-        for (int64_t a = 0; a < nb * n; a += chunk) {
-          const int64_t b = std::min(a + chunk, nb * n);
-          MSBFS_HIP_CHECK(hipMemcpyAsync(pin, dev + a, (size_t)(b - a) * sizeof(int32_t),
-                                         hipMemcpyDeviceToHost, hs));
-          MSBFS_HIP_CHECK(hipStreamSynchronize(hs));
-          msbfs::dist_scatter_flat(pin, a, b, n, ld, dist_host + k0 * ld);
-        }
+        msbfs::dist_stage_download(pinned_copy(dev, pin, hs), nb, n, chunk, ld, pin,
+                                   dist_host + k0 * ld);
       }
     });
   });
@@ -510,6 +519,77 @@ int msbfs_cpu_run_dist(int64_t n, const int64_t* rowptr, const int32_t* col, int
     q.ids.assign(qids, qids + qoff[K]);
     std::vector<int64_t> f;
     msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, dist, ld);
+    std::memcpy(F, f.data(), K * sizeof(int64_t));
+  });
+}
+
+int msbfs_parents_wide_degree(void) { return msbfs::kParentsWideDegree; }
+
+int msbfs_solver_run_parents(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
+                             int64_t* F, void* dist_dev, void* parent_dev, int64_t ld,
+                             msbfs_stats* st, void* stream) {
+  return guard([&] {
+    check_dist_args(s, K, qoff, qids, F, dist_dev, ld);
+    if (K > 0 && !parent_dev) msbfs::fail("run_parents: no parent output");
+    timed(s, stream, st, "solver run_parents", [&](msbfs::RunStats* rs, hipStream_t hs) {
+      if (K > 0)
+        s->impl->run_parents(K, qoff, qids, F, (int32_t*)dist_dev, (int32_t*)parent_dev, ld, rs, hs);
+    });
+  });
+}
+
+int msbfs_solver_run_parents_host(msbfs_solver s, int64_t K, const int64_t* qoff,
+                                  const int32_t* qids, int64_t* F, int32_t* dist_host,
+                                  int32_t* parent_host, int64_t ld, msbfs_stats* st,
+                                  void* stream) {
+  return guard([&] {
+    check_dist_args(s, K, qoff, qids, F, dist_host, ld);
+    if (K > 0 && !parent_host) msbfs::fail("run_parents: no parent output");
+    const int64_t n = s->graph->g.n;
+    timed(s, stream, st, "solver run_parents_host", [&](msbfs::RunStats* rs, hipStream_t hs) {
+      if (K <= 0) return;
+      // (two staged matrices: each gets half of the per-group solvers' byte budget)
+      const int64_t rows =
+          msbfs::dist_stage_rows(s->impl->pass_groups(), K, n, kDistStageBudget / 2);
+      const size_t stage_bytes = (size_t)rows * std::max<int64_t>(n, 1) * sizeof(int32_t);
+      s->dist_stage.ensure(stage_bytes);
+      s->parent_stage.ensure(stage_bytes);
+      const int64_t chunk =
+          std::min<int64_t>(kDistPinnedBytes / (int64_t)sizeof(int32_t), std::max<int64_t>(rows * n, 1));
+      if (!s->dist_pinned || s->dist_pinned->bytes < (size_t)chunk * sizeof(int32_t))
+        s->dist_pinned = std::make_unique<msbfs::PinnedBuf>((size_t)chunk * sizeof(int32_t));
+      int32_t* pin = s->dist_pinned->as<int32_t>();
+      int32_t* const dev[2] = {s->dist_stage.as<int32_t>(), s->parent_stage.as<int32_t>()};
+      int32_t* const host[2] = {dist_host, parent_host};
+      for (int64_t k0 = 0; k0 < K; k0 += rows) {
+        const int64_t nb = std::min(rows, K - k0);
+        s->impl->run_parents(nb, qoff + k0, qids, F + k0, dev[0], dev[1], n, rs, hs);
+        for (int m = 0; m < 2; ++m)
+          msbfs::dist_stage_download(pinned_copy(dev[m], pin, hs), nb, n, chunk, ld, pin,
+                                     host[m] + k0 * ld);
+      }
+    });
+  });
+}
+
+int msbfs_cpu_run_parents(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
+                          const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist,
+                          int32_t* parent, int64_t ld, int nthreads) {
+  return guard([&] {
+    if (n < 0 || K < 0 || (K > 0 && (!qoff || !F || !dist || !parent)))
+      msbfs::fail("cpu_run_parents: bad arguments");
+    if (ld < n) msbfs::fail("cpu_run_parents: ld must be at least n");
+    if (K == 0) return;
+    msbfs::HostCsr g;
+    g.n = n;
+    g.rowptr.assign(rowptr, rowptr + n + 1);
+    g.col.assign(col, col + rowptr[n]);
+    g.m = rowptr[n] / 2;
+    msbfs::QuerySet q;
+    q.off.assign(qoff, qoff + K + 1);
+    q.ids.assign(qids, qids + qoff[K]);
+    std::vector<int64_t> f;
+    msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, dist, ld, parent);
     std::memcpy(F, f.data(), K * sizeof(int64_t));
   });
 }

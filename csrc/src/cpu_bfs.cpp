@@ -44,8 +44,25 @@ int64_t cpu_msbfs_F(const HostCsr& g, const int32_t* src, int64_t nsrc, std::vec
   return F;
 }
 
+void cpu_parent_row(const HostCsr& g, const int32_t* dist, int32_t* parent) {
+  for (int64_t v = 0; v < g.n; ++v) {
+    const int32_t d = dist[v];
+    int32_t p = d == 0 ? (int32_t)v : -1;
+    if (d > 0) {
+      for (int64_t j = g.rowptr[v], e = g.rowptr[v + 1]; j < e; ++j) {
+        if (dist[g.col[j]] == d - 1) {
+          p = g.col[j];
+          break;
+        }
+      }
+    }
+    parent[v] = p;
+  }
+}
+
 void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
-                   std::vector<int64_t>* edges, int nthreads, int32_t* dist_out, int64_t ld) {
+                   std::vector<int64_t>* edges, int nthreads, int32_t* dist_out, int64_t ld,
+                   int32_t* parent_out) {
   const int64_t K = q.K();
   F.assign(K, 0);
   if (edges) edges->assign(K, 0);
@@ -63,6 +80,7 @@ void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
       if (edges) (*edges)[k] = e;
       // (the worker's distance array already is the row: -1 unreached, 0 the valid sources)
       if (dist_out) std::copy(dist.begin(), dist.begin() + g.n, dist_out + k * ld);
+      if (parent_out) cpu_parent_row(g, dist.data(), parent_out + k * ld);
     }
   };
   if (nthreads == 1) {

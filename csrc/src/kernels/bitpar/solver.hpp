@@ -33,7 +33,7 @@
 //   bitpar/bits.hpp                      pure bit helpers (HIP-free, pinned by the host self-test)
 //   bitpar/common.hpp  init.hpp  push.hpp  hybrid.hpp  tiles.hpp      kernels by family; the pull
 //   bitpar/pull.hpp  pull_full.hpp  pull_lists.hpp  pull_tail.hpp     levels': pulls, lists, tail push
-//   bitpar/record.hpp                    the distance output of run_dist (per-level record kernels)
+//   bitpar/record.hpp                    the distance / parent output of run_dist, run_parents (per level)
 //   bitpar_solver.hip  construction, batches, the level loop (direction choice, reductions)
 //   bitpar_push.hip    top-down levels and the device-driven level batches
 //   bitpar_pull.hip    bottom-up levels (prefix pull + tail push, narrow / lean / chunk pulls),
@@ -85,6 +85,10 @@ class BitparSolver final : public Solver {
   // run() plus dist_dev[k * ld + v] (bitpar/record.hpp); forces the edge-counting instantiation
   void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
                 int64_t ld, RunStats* st, hipStream_t stream) override;
+  // run_dist() plus parent_dev[k * ld + v], the first-in-row BFS parent (bitpar/record.hpp)
+  void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                   int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
+                   hipStream_t stream) override;
   void tune(const std::string& spec) override { tun_.parse(spec); }
   int64_t pass_groups() const override { return 64 * (int64_t)std::min(maxW_, opt.max_words); }
   // graph-derived tables and worst-case scratch, built before any timed run (bitpar_pull.hip)
@@ -447,14 +451,20 @@ class BitparSolver final : public Solver {
   DevBuf bctr_;  // (kBatch+1) Ctr slots, then (kBatch+1) x 16 alive words
   // ---- distance output (bitpar/record.hpp)
   Record rec_;     // set by run_dist for its duration; rec_.out == nullptr otherwise
-  DevBuf n2o_;     // inverse of g_.old2new, built on first use, cached per map
+  InverseMap n2o_;  // inverse of g_.old2new, built on first use, cached per map
   DevBuf rslot_;   // the dense walk's marks (record.hpp), n int32, zero between levels
-  const void* n2o_key_ = nullptr;
-  const int32_t* new2old(hipStream_t s);
+  DevBuf seen_;    // a parents run's seen rows (record.hpp), n * W words, zeroed per batch
+  DevBuf wq_;      // its wide queue: a counter (first 16 bytes), then n vertex ids
+  void run_dist_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                     int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
+                     hipStream_t stream);
   // the level-0 zeros of a batch's source pairs / one level's new bits off the new frontier list
   // fl_[fc ^ 1] (length from ctr; new bits = a, or a & ~b with DIFF), right after the level's
-  // k_count_frontier. Both launch nothing unless a distance run is under way.
-  void record_sources(const int32_t* pv, const int32_t* pk, int64_t np, hipStream_t s);
+  // k_count_frontier. Both launch nothing unless a distance run is under way; in a parents run
+  // (rec_.parent) they also store the parents: the sources' own ids, and per level the search
+  // against the seen rows that entered the level (narrow vertices, then the queued wide ones),
+  // then the commit of the level's bits to them.
+  void record_sources(const int32_t* pv, const int32_t* pk, int64_t np, int w, hipStream_t s);
   template <int W, bool DIFF>
   void record_level(const int32_t* fl, const Ctr* ctr, const uint64_t* a, const uint64_t* b,
                     int64_t nmax, int grid_cap, uint32_t level, hipStream_t s,
@@ -468,6 +478,19 @@ class BitparSolver final : public Solver {
     k_record_levels<W, DIFF><<<grid_for(dense ? g_.n : nmax, kBlock, grid_cap), kBlock, 0, s>>>(
         fl, ctr, a, b, rec_.new2old, dense ? rec_.slot : nullptr, g_.n,
         rec_.out + rec_.k0 * rec_.ld, rec_.ld, rec_.nb, (int32_t)level);
+    MSBFS_HIP_CHECK(hipGetLastError());
+    if (!rec_.parent) return;
+    k_record_parents<W, DIFF><<<grid_for(nmax, Lay<W>::TILE, grid_cap), kBlock, 0, s>>>(
+        fl, ctr, a, b, g_.rowptr, g_.col, rec_.seen, rec_.new2old, g_.n,
+        rec_.parent + rec_.k0 * rec_.ld, rec_.ld, rec_.nb, rec_.wq, rec_.wcnt);
+    // (the queue's length is known on the device only: a block per queued vertex, grid-stride;
+    // no launch on a graph that has no wide vertex, so none in the device-driven push batches)
+    if (g_.max_degree >= kRecordWideDeg)
+      k_record_parents_wide<W, DIFF><<<grid_for(nmax, 1, grid_cap), kBlock, 0, s>>>(
+          rec_.wq, rec_.wcnt, a, b, g_.rowptr, g_.col, rec_.seen, rec_.new2old, g_.n,
+          rec_.parent + rec_.k0 * rec_.ld, rec_.ld, rec_.nb);
+    k_record_commit<W, DIFF><<<grid_for(nmax * W, kBlock, grid_cap), kBlock, 0, s>>>(
+        fl, ctr, a, b, g_.n, rec_.seen, rec_.wcnt);
     MSBFS_HIP_CHECK(hipGetLastError());
   }
   std::unique_ptr<PinnedBuf> hbctr_;

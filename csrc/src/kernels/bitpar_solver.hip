@@ -76,51 +76,51 @@ void BitparSolver::run(int64_t K, const int64_t* qoff, const int32_t* qids, int6
 }
 
 // ---- distance output (bitpar/record.hpp) --------------------------------------------------------
-// new2old[old2new[v]] = v (old2new is a permutation of [0, n))
-static __global__ __launch_bounds__(kBlock) void k_invert_map(const int32_t* old2new, int64_t n,
-                                                              int32_t* new2old) {
-  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n;
-       v += (int64_t)gridDim.x * kBlock) {
-    const int32_t w = old2new[v];
-    if (w >= 0 && w < n) new2old[w] = (int32_t)v;
-  }
-}
-
 // Level 0: the batch's (source, local group) pairs, original ids, range-checked by start_batch.
-// Duplicates store the same zero twice. out: row 0 = the batch's first group.
-static __global__ __launch_bounds__(kBlock) void k_record_sources(const int32_t* pv,
-                                                                  const int32_t* pk, int64_t np,
-                                                                  int64_t n, int64_t nb,
-                                                                  int32_t* out, int64_t ld) {
+// Duplicates store the same zero twice. out: row 0 = the batch's first group. parent != nullptr
+// (a parents run): the source is its own parent, and its bit goes into seen (w words per
+// vertex, internal ids) with an atomic: several pairs can share a word.
+static __global__ __launch_bounds__(kBlock) void k_record_sources(
+    const int32_t* pv, const int32_t* pk, int64_t np, int64_t n, int64_t nb, int32_t* out,
+    int64_t ld, int32_t* parent, uint64_t* seen, const int32_t* old2new, int w) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < np;
        i += (int64_t)gridDim.x * kBlock) {
     const int32_t v = pv[i], k = pk[i];
-    if (v >= 0 && v < n && k >= 0 && k < nb) out[(int64_t)k * ld + v] = 0;
+    if (!(v >= 0 && v < n && k >= 0 && k < nb)) continue;
+    out[(int64_t)k * ld + v] = 0;
+    if (!parent) continue;
+    parent[(int64_t)k * ld + v] = v;
+    const int32_t iv = old2new ? old2new[v] : v;
+    if (iv >= 0 && iv < n && (k >> 6) < w)
+      atomicOr((unsigned long long*)&seen[(int64_t)iv * w + (k >> 6)], 1ull << (k & 63));
   }
 }
 
-const int32_t* BitparSolver::new2old(hipStream_t s) {
-  if (!g_.old2new) return nullptr;
-  if (n2o_key_ != (const void*)g_.old2new) {
-    n2o_.ensure((size_t)std::max<int64_t>(g_.n, 1) * sizeof(int32_t));
-    k_invert_map<<<grid_for(g_.n, kBlock, 2048), kBlock, 0, s>>>(g_.old2new, g_.n,
-                                                                 n2o_.as<int32_t>());
-    MSBFS_HIP_CHECK(hipGetLastError());
-    n2o_key_ = g_.old2new;
-  }
-  return n2o_.as<int32_t>();
-}
-
-void BitparSolver::record_sources(const int32_t* pv, const int32_t* pk, int64_t np,
+void BitparSolver::record_sources(const int32_t* pv, const int32_t* pk, int64_t np, int w,
                                   hipStream_t s) {
   if (!rec_.out || np <= 0) return;
   k_record_sources<<<grid_for(np, kBlock), kBlock, 0, s>>>(
-      pv, pk, np, g_.n, rec_.nb, rec_.out + rec_.k0 * rec_.ld, rec_.ld);
+      pv, pk, np, g_.n, rec_.nb, rec_.out + rec_.k0 * rec_.ld, rec_.ld,
+      rec_.parent ? rec_.parent + rec_.k0 * rec_.ld : nullptr, rec_.seen, g_.old2new, w);
   MSBFS_HIP_CHECK(hipGetLastError());
 }
 
 void BitparSolver::run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
                             int32_t* dist_dev, int64_t ld, RunStats* st, hipStream_t stream) {
+  run_dist_impl(K, qoff, qids, F, dist_dev, nullptr, ld, st, stream);
+}
+
+void BitparSolver::run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                               int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
+                               hipStream_t stream) {
+  if (!parent_dev) fail("run_parents: no parent output");
+  run_dist_impl(K, qoff, qids, F, dist_dev, parent_dev, ld, st, stream);
+}
+
+// parent_dev != nullptr: a parents run
+void BitparSolver::run_dist_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                                 int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
+                                 hipStream_t stream) {
   const int64_t n = g_.n;
   if (!dist_dev) fail("run_dist: no distance output");
   if (ld < n) fail("run_dist: ld must be at least n");
@@ -131,7 +131,7 @@ void BitparSolver::run_dist(int64_t K, const int64_t* qoff, const int32_t* qids,
   } scope{rec_};
   rec_.out = dist_dev;
   rec_.ld = ld;
-  rec_.new2old = new2old(stream);
+  rec_.new2old = n2o_.get(g_, stream);
   if (rec_.new2old && n > 0) {
     // (zeroed per run: a run that failed half way may have left marks)
     rslot_.ensure((size_t)n * sizeof(int32_t));
@@ -140,18 +140,33 @@ void BitparSolver::run_dist(int64_t K, const int64_t* qoff, const int32_t* qids,
   }
   const int64_t builds0 = plen_builds_;
   const int mw = std::min(maxW_, opt.max_words);
+  const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+  if (parent_dev) {
+    seen_.ensure(n1 * mw * sizeof(uint64_t));
+    rec_.parent = parent_dev;
+    rec_.seen = seen_.as<uint64_t>();
+    wq_.ensure(16 + n1 * sizeof(int32_t));
+    // (zeroed per run: a run that failed half way may have left a count)
+    MSBFS_HIP_CHECK(hipMemsetAsync(wq_.p, 0, 16, stream));
+    rec_.wcnt = wq_.as<uint32_t>();
+    rec_.wq = wq_.as<int32_t>() + 4;
+  }
   for (Batch b = batch_at(K, 0, mw); b.k0 < K; b = batch_at(K, b.k0 + b.nb, mw)) {
     rec_.k0 = b.k0;
     rec_.nb = b.nb;
     // the -1 fill of the pass's rows, columns [0, n) only
-    if (n > 0) {
-      int32_t* rows = dist_dev + b.k0 * ld;
+    for (int32_t* m : {dist_dev, parent_dev}) {
+      if (!m || n <= 0) continue;
+      int32_t* rows = m + b.k0 * ld;
       if (ld == n)
         MSBFS_HIP_CHECK(hipMemsetAsync(rows, 0xFF, (size_t)b.nb * n * sizeof(int32_t), stream));
       else
         MSBFS_HIP_CHECK(hipMemset2DAsync(rows, (size_t)ld * sizeof(int32_t), 0xFF,
                                          (size_t)n * sizeof(int32_t), (size_t)b.nb, stream));
     }
+    // (the batch's seen rows: b.w words per vertex)
+    if (parent_dev)
+      MSBFS_HIP_CHECK(hipMemsetAsync(seen_.p, 0, n1 * b.w * sizeof(uint64_t), stream));
     run_batch(b.w, b.k0, b.nb, qoff, qids, F + b.k0, nullptr, st, stream);
     if (st) st->batches++;
   }
@@ -242,7 +257,7 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
         acc_[S.ac].as<uint64_t>(), stamp_.as<int32_t>(), epoch_, fl_[S.fc].as<int32_t>(),
         ctr_.as<Ctr>(), sm.E, sm.alive[0], anyvis_.as<uint32_t>(), g_.old2new);
     MSBFS_HIP_CHECK(hipGetLastError());
-    if constexpr (COUNT) record_sources(dpv, dpk, np, s);  // (a distance run's level 0)
+    if constexpr (COUNT) record_sources(dpv, dpk, np, W, s);  // (a distance run's level 0)
   }
   const HostCtr c = read_ctr(s);  // also retires the pinned/host source copies
   S.nf = c.fl2;

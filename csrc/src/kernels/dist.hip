@@ -360,6 +360,72 @@ static void check_dist_out(const DeviceGraph& g, const int32_t* dist_dev, int64_
   if (ld < g.n) fail("run_dist: ld must be at least n");
 }
 
+// Parent output (Solver::run_parents): one group's row from the solver's own distance array,
+// over the internal ids i: out[user id of i] = -1 where unreached, the user's id itself for a
+// source, else the user's id of the first entry u of i's row with dist[u] == dist[i] - 1. Every
+// column below n is written. Rows from kParentsWideDegree entries on are scanned by the whole
+// wave, 64 entries per step, the lowest hitting lane giving the parent (a hub reached at level 1
+// finds its source far down a degree-sorted row).
+__global__ __launch_bounds__(kBlock) void k_parent_row(const int32_t* dist, const int64_t* rowptr,
+                                                       const int32_t* col,
+                                                       const int32_t* new2old, int64_t n,
+                                                       int32_t* out) {
+  const int lane = lane_id();
+  for (int64_t base = (int64_t)blockIdx.x * kBlock; base < n; base += (int64_t)gridDim.x * kBlock) {
+    const int64_t i = base + threadIdx.x;
+    int32_t d = -1, o = 0;
+    int64_t rb = 0, re = 0;
+    if (i < n) {
+      d = dist[i];
+      o = new2old ? new2old[i] : (int32_t)i;
+      rb = rowptr[i];
+      re = rowptr[i + 1];
+    }
+    const bool wide = i < n && d > 0 && re - rb >= kParentsWideDegree;
+    if (i < n && !wide) {
+      int32_t p = -1;
+      if (d == 0) p = o;
+      if (d > 0) {
+        for (int64_t e = rb; e < re; ++e) {
+          const int32_t u = col[e];
+          if (u >= 0 && u < n && dist[u] == d - 1) {
+            p = new2old ? new2old[u] : u;
+            break;
+          }
+        }
+      }
+      out[o] = p;
+    }
+    uint64_t wm = __ballot(wide);
+    while (wm) {
+      const int l = __ffsll((unsigned long long)wm) - 1;
+      wm &= wm - 1;
+      const int64_t wb = __shfl((long long)rb, l), we = __shfl((long long)re, l);
+      const int32_t wd = __shfl(d, l), wo = __shfl(o, l);
+      int32_t p = -1;  // (stays -1 only if the distances are not a BFS labelling)
+      for (int64_t q = wb; q < we; q += 64) {
+        const int64_t e = q + lane;
+        const int32_t u = e < we ? col[e] : -1;
+        const bool hit = u >= 0 && u < n && dist[u] == wd - 1;
+        const uint64_t m = __ballot(hit);
+        if (m) {
+          const int32_t pu = hit ? (new2old ? new2old[u] : u) : -1;
+          p = __shfl(pu, __ffsll((unsigned long long)m) - 1);
+          break;
+        }
+      }
+      if (lane == 0) out[wo] = p;
+    }
+  }
+}
+static void parent_row(const DeviceGraph& g, const int32_t* dist, const int32_t* new2old,
+                       int32_t* out_row, hipStream_t s) {
+  if (g.n <= 0) return;
+  k_parent_row<<<grid_for(g.n, kBlock, 4096), kBlock, 0, s>>>(dist, g.rowptr, g.col, new2old, g.n,
+                                                              out_row);
+  MSBFS_HIP_CHECK(hipGetLastError());
+}
+
 // the first launch of a kernel of this unit loads its code object (1.5-2.8 ms, see
 // bp::load_code_objects): prepare() does it before any timed run
 static __global__ void k_load_dist() {}
@@ -392,19 +458,27 @@ class DistSolver final : public Solver {
 
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
            RunStats* st, hipStream_t s) override {
-    run_impl(K, qoff, qids, F, edges2, nullptr, 0, st, s);
+    run_impl(K, qoff, qids, F, edges2, nullptr, nullptr, 0, st, s);
   }
   void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
                 int64_t ld, RunStats* st, hipStream_t s) override {
     check_dist_out(g_, dist_dev, ld);
-    run_impl(K, qoff, qids, F, nullptr, dist_dev, ld, st, s);
+    run_impl(K, qoff, qids, F, nullptr, dist_dev, nullptr, ld, st, s);
+  }
+  void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                   int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
+                   hipStream_t s) override {
+    check_dist_out(g_, dist_dev, ld);
+    if (!parent_dev) fail("run_parents: no parent output");
+    run_impl(K, qoff, qids, F, nullptr, dist_dev, parent_dev, ld, st, s);
   }
 
  private:
   // dout != nullptr: row k of it gets group k's distances (gathered before the next group's
-  // lazy reset scatters -1 over them)
+  // lazy reset scatters -1 over them); pout != nullptr: row k of it the parents, likewise
   void run_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
-                int32_t* dout, int64_t ld, RunStats* st, hipStream_t s) {
+                int32_t* dout, int32_t* pout, int64_t ld, RunStats* st, hipStream_t s) {
+    const int32_t* n2o = pout ? inv_.get(g_, s) : nullptr;
     const int64_t n = g_.n;
     int64_t maxs = 1;
     for (int64_t k = 0; k < K; ++k) maxs = std::max(maxs, qoff[k + 1] - qoff[k]);
@@ -539,6 +613,7 @@ class DistSolver final : public Solver {
         if (st) st->levels++;
       }
       if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
+      if (pout) parent_row(g_, dist_.as<int32_t>(), n2o, pout + k * ld, s);
       visited_ = lo + nf;  // every visited vertex sits in ord[0, lo + nf)
       F[k] = Fk;
       if (edges2) edges2[k] = E2;
@@ -554,6 +629,7 @@ class DistSolver final : public Solver {
   const DeviceGraph& g_;
   DevBuf dist_, ord_, ul_[2], ulw_[2], offs_, scan_tmp_, ctr_, src_, slots_;
   size_t scan_bytes_ = 0;
+  InverseMap inv_;
   int64_t visited_ = 0;  // vertices the last group reached (ord[0, visited_) to reset)
   std::unique_ptr<PinnedBuf> hctr_, hslots_;
 };
@@ -571,17 +647,25 @@ class SweepSolver final : public Solver {
   }
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
            RunStats* st, hipStream_t s) override {
-    run_impl(K, qoff, qids, F, edges2, nullptr, 0, st, s);
+    run_impl(K, qoff, qids, F, edges2, nullptr, nullptr, 0, st, s);
   }
   void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
                 int64_t ld, RunStats* st, hipStream_t s) override {
     check_dist_out(g_, dist_dev, ld);
-    run_impl(K, qoff, qids, F, nullptr, dist_dev, ld, st, s);
+    run_impl(K, qoff, qids, F, nullptr, dist_dev, nullptr, ld, st, s);
+  }
+  void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                   int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
+                   hipStream_t s) override {
+    check_dist_out(g_, dist_dev, ld);
+    if (!parent_dev) fail("run_parents: no parent output");
+    run_impl(K, qoff, qids, F, nullptr, dist_dev, parent_dev, ld, st, s);
   }
 
  private:
   void run_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
-                int32_t* dout, int64_t ld, RunStats* st, hipStream_t s) {
+                int32_t* dout, int32_t* pout, int64_t ld, RunStats* st, hipStream_t s) {
+    const int32_t* n2o = pout ? inv_.get(g_, s) : nullptr;
     const int64_t n = g_.n;
     int64_t maxs = 1;
     for (int64_t k = 0; k < K; ++k) maxs = std::max(maxs, qoff[k + 1] - qoff[k]);
@@ -623,11 +707,13 @@ class SweepSolver final : public Solver {
       F[k] = (int64_t)h[0];
       if (edges2) edges2[k] = (int64_t)h[1];
       if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
+      if (pout) parent_row(g_, dist_.as<int32_t>(), n2o, pout + k * ld, s);
     }
   }
 
   const DeviceGraph& g_;
   DevBuf dist_, fl_, ctr_, red_, src_;
+  InverseMap inv_;
   std::unique_ptr<PinnedBuf> hctr_;
 };
 

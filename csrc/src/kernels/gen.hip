@@ -721,6 +721,29 @@ void frontier_degree_scan(const int64_t* rowptr, const int32_t* list, int64_t cn
   MSBFS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(t2, tb, degs, offs, (int)cnt, s));
 }
 
+namespace {
+// new2old[old2new[v]] = v (old2new is a permutation of [0, n))
+__global__ __launch_bounds__(256) void k_invert_map(const int32_t* old2new, int64_t n,
+                                                    int32_t* new2old) {
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t w = old2new[v];
+    if (w >= 0 && w < n) new2old[w] = (int32_t)v;
+  }
+}
+}  // namespace
+
+const int32_t* InverseMap::get(const DeviceGraph& g, hipStream_t s) {
+  if (!g.old2new) return nullptr;
+  if (key != (const void*)g.old2new) {
+    buf.ensure((size_t)std::max<int64_t>(g.n, 1) * sizeof(int32_t));
+    k_invert_map<<<grid_for(g.n, 256, 2048), 256, 0, s>>>(g.old2new, g.n, buf.as<int32_t>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+    key = g.old2new;
+  }
+  return buf.as<int32_t>();
+}
+
 size_t inclusive_scan_temp_bytes(int64_t max_items) {
   size_t tb = 0;
   MSBFS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (int64_t*)nullptr,

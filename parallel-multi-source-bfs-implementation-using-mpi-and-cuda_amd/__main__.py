@@ -21,6 +21,7 @@ def main(argv=None) -> int:
     cfg = JobConfig()
     json_out = False
     dist_out = None  # --dist-out FILE: the winning group's distance row (n x int32 LE)
+    parent_out = None  # --parent-out FILE: its BFS parent row (n x int32 LE)
     i = 1
     while i < len(argv):
         a = argv[i]
@@ -48,6 +49,8 @@ def main(argv=None) -> int:
             cfg.count_edges = True
         elif a == "--dist-out" and has:
             dist_out = argv[i + 1]; i += 1
+        elif a == "--parent-out" and has:
+            parent_out = argv[i + 1]; i += 1
         i += 1
     if cfg.num_gpu <= 0:
         print("msbfs: -gn must be >= 1", file=sys.stderr)
@@ -72,10 +75,13 @@ def main(argv=None) -> int:
                               "backend": ctx.backend, "traversed_edges": r.traversed_edges,
                               "F": [int(x) for x in r.F]}))
         sys.stdout.flush()
-        if dist_out is not None:  # after the report, outside the computation time
-            row = eng.winner_distances(r)
-            if row is not None:
+        if dist_out is not None or parent_out is not None:
+            # after the report, outside the computation time
+            row, prow = eng.winner_rows(r, parents=parent_out is not None)
+            if row is not None and dist_out is not None:
                 row.astype("<i4").tofile(dist_out)
+            if prow is not None:
+                prow.astype("<i4").tofile(parent_out)
     eng.close()
     D.shutdown(ctx)
     return 0

@@ -167,23 +167,29 @@ class Engine:
             edges = int(D.allreduce_sum_i64(np.array([int(res.edges.sum())], np.int64), ctx)[0])
         return JobResult(min_k, min_f, self.preprocessing_time, dt, F, edges, res.stats)
 
-    def winner_distances(self, r: JobResult) -> Optional[np.ndarray]:
-        """The winning group's distance row (int32[n], original vertex ids, -1 unreached), or
-        None when there is no winner (K = 0). Outside the computation boundary: the per-group
+    def winner_rows(self, r: JobResult, parents: bool = False):
+        """The winning group's (distance row, parent row): int32[n] each, original vertex ids, -1
+        unreached; the parent row (see Solver.parents) only with parents=True, else None. (None,
+        None) when there is no winner (K = 0). Outside the computation boundary: the per-group
         distance solver for one group on device algorithms, the CPU path for --algo cpu."""
         if self.queries.K == 0 or r.min_k < 0:
-            return None
+            return None, None
         q = self.queries.subset(np.array([r.min_k], np.int64))
         if self.on_gpu:
             with Solver(self.dgraph, "dist", max_groups=1) as s:
-                res = s.distances(q)
+                res = s.parents(q) if parents else s.distances(q)
         else:
             g = self.graph_host if self.graph_host is not None else self.dgraph.download()
-            res = cpu_bfs(g, q, distances=True)
+            res = cpu_bfs(g, q, distances=True, parents=parents)
         if int(res.F[0]) != int(r.min_f):
-            raise RuntimeError(f"the winner's distance row sums to {int(res.F[0])}, not to its "
-                               f"F {int(r.min_f)}")
-        return res.dist[0]
+            what = "parents" if parents else "distance"
+            raise RuntimeError(f"the winner's {what} run: its distance row sums to "
+                               f"{int(res.F[0])}, not to its F {int(r.min_f)}")
+        return res.dist[0], (res.parent[0] if parents else None)
+
+    def winner_distances(self, r: JobResult) -> Optional[np.ndarray]:
+        """The winning group's distance row (see winner_rows)."""
+        return self.winner_rows(r)[0]
 
     def report(self, r: JobResult) -> str:
         return format_report(self.cfg.graph or self.cfg.gen or "", self.cfg.query or self.cfg.qgen or "",

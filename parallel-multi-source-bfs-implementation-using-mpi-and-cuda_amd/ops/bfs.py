@@ -32,6 +32,9 @@ class BfsResult:
     # int32[K, n] per-vertex distances (original vertex ids; -1 unreached) of a distances() /
     # distances=True call; None otherwise, and when they went to a device buffer (out_ptr)
     dist: Optional[np.ndarray] = None
+    # int32[K, n] BFS parents (original vertex ids; a source is its own parent, -1 unreached) of
+    # a parents() / parents=True call; None otherwise, and when they went to device buffers
+    parent: Optional[np.ndarray] = None
 
 
 def _host_dist_out(K: int, n: int, out: Optional[np.ndarray], ld: Optional[int]):
@@ -143,6 +146,45 @@ class Solver:
                                                       native.ptr(D, C.c_int32), ld, C.byref(st),
                                                       sp))
         return BfsResult(F, None, st.as_dict(), D[:, :n])
+
+    def parents(self, queries: QuerySet, dist_ptr: Optional[int] = None,
+                parent_ptr: Optional[int] = None, ld: Optional[int] = None,
+                stream: Optional[int] = None) -> BfsResult:
+        """F, the distances (as distances()) and the BFS parents of every group: parent[k, v] = v
+        for the valid sources of group k, -1 where unreached, otherwise the first neighbour u of
+        v with dist[k, u] == dist[k, v] - 1, "first" in the order of v's row in the device graph
+        (graph.download(), internal ids, mapped back through graph.relabel_map()). All device
+        solvers return the same matrix on one DeviceGraph; path_to_set / nearest_source read it.
+
+        Host output (default): BfsResult.dist and .parent are int32[K, ld or n][:, :n].
+        dist_ptr and parent_ptr: integer device addresses of K x ld int32 each (ld defaults to
+        n) that receive the rows instead; BfsResult.dist and .parent are None. One pointer
+        without the other raises ValueError."""
+        if (dist_ptr is None) != (parent_ptr is None):
+            raise ValueError("give both dist_ptr and parent_ptr (device) or neither (host)")
+        K = queries.K
+        n = self.graph.n
+        F = np.zeros(K, dtype=np.int64)
+        st = native.Stats()
+        L = native.lib()
+        sp = C.c_void_p(stream) if stream else None
+        qo, qi = native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32)
+        if dist_ptr is not None:
+            ld = n if ld is None else int(ld)
+            if ld < n:
+                raise ValueError("ld must be at least n")
+            if K:
+                native.check(L.msbfs_solver_run_parents(
+                    self._h, K, qo, qi, native.ptr(F, C.c_int64), C.c_void_p(int(dist_ptr)),
+                    C.c_void_p(int(parent_ptr)), ld, C.byref(st), sp))
+            return BfsResult(F, None, st.as_dict(), None, None)
+        D, ld = _host_dist_out(K, n, None, ld)
+        Pm = np.full((K, ld), -1, dtype=np.int32)
+        if K:
+            native.check(L.msbfs_solver_run_parents_host(
+                self._h, K, qo, qi, native.ptr(F, C.c_int64), native.ptr(D, C.c_int32),
+                native.ptr(Pm, C.c_int32), ld, C.byref(st), sp))
+        return BfsResult(F, None, st.as_dict(), D[:, :n], Pm[:, :n])
 
     def level_trace(self) -> list:
         """Per-level records of the last run / hybrid phase (bit-parallel solver): batch, level,
@@ -269,23 +311,30 @@ class Solver:
 
 
 def cpu_bfs(graph: Graph, queries: QuerySet, threads: int = 0, count_edges: bool = False,
-            distances: bool = False, out: Optional[np.ndarray] = None) -> BfsResult:
+            distances: bool = False, out: Optional[np.ndarray] = None,
+            parents: bool = False) -> BfsResult:
     """Query-parallel host BFS (native C++ threads). distances=True: BfsResult.dist is the
-    int32[K, n] distance matrix (see Solver.distances; `out` as there)."""
+    int32[K, n] distance matrix (see Solver.distances; `out` as there). parents=True: the
+    distances plus BfsResult.parent, the int32[K, n] BFS parents (see Solver.parents; "first
+    neighbour" in the row order of `graph`)."""
     K = queries.K
     F = np.zeros(K, dtype=np.int64)
     E = np.zeros(K, dtype=np.int64) if count_edges else None
-    if distances:
+    if distances or parents:
         D, ld = _host_dist_out(K, graph.n, out, None)
-        if K:
-            native.check(native.lib().msbfs_cpu_run_dist(
-                graph.n, native.ptr(graph.rowptr, C.c_int64), native.ptr(graph.col, C.c_int32), K,
-                native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32),
-                native.ptr(F, C.c_int64), native.ptr(D, C.c_int32), ld, int(threads)))
+        Pm = np.full((K, ld), -1, dtype=np.int32) if parents else None
+        ga = (graph.n, native.ptr(graph.rowptr, C.c_int64), native.ptr(graph.col, C.c_int32), K,
+              native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32),
+              native.ptr(F, C.c_int64), native.ptr(D, C.c_int32))
+        if K and parents:
+            native.check(native.lib().msbfs_cpu_run_parents(*ga, native.ptr(Pm, C.c_int32), ld,
+                                                            int(threads)))
+        elif K:
+            native.check(native.lib().msbfs_cpu_run_dist(*ga, ld, int(threads)))
         if E is not None and K:
             deg = np.diff(graph.rowptr)
             E[:] = [int(deg[D[k, :graph.n] >= 0].sum()) // 2 for k in range(K)]
-        return BfsResult(F, E, {}, D[:, :graph.n])
+        return BfsResult(F, E, {}, D[:, :graph.n], None if Pm is None else Pm[:, :graph.n])
     if K:
         native.check(native.lib().msbfs_cpu_run(
             graph.n, native.ptr(graph.rowptr, C.c_int64), native.ptr(graph.col, C.c_int32), K,
@@ -297,22 +346,58 @@ def cpu_bfs(graph: Graph, queries: QuerySet, threads: int = 0, count_edges: bool
 
 def multi_source_bfs(graph: Union[Graph, DeviceGraph], queries: QuerySet, algo: str = "auto",
                      device: int = 0, count_edges: bool = False, distances: bool = False,
-                     **opts) -> BfsResult:
+                     parents: bool = False, **opts) -> BfsResult:
     """One-shot convenience wrapper (creates and frees a Solver). distances=True: the result
-    also carries the int32[K, n] distance matrix (Solver.distances); the traversed-edge counts
-    then come from a second, plain run when count_edges is set too."""
+    also carries the int32[K, n] distance matrix (Solver.distances); parents=True: that and the
+    BFS parent matrix (Solver.parents). The traversed-edge counts then come from a second,
+    plain run when count_edges is set too."""
     if algo == "cpu":
         if isinstance(graph, DeviceGraph):
             graph = graph.download()
-        return cpu_bfs(graph, queries, count_edges=count_edges, distances=distances)
+        return cpu_bfs(graph, queries, count_edges=count_edges, distances=distances,
+                       parents=parents)
     dg = graph if isinstance(graph, DeviceGraph) else DeviceGraph.from_host(graph, device)
     with Solver(dg, algo, max_groups=max(1, queries.K), **opts) as s:
-        if not distances:
+        if not distances and not parents:
             return s.run(queries, count_edges=count_edges)
-        r = s.distances(queries)
+        r = s.parents(queries) if parents else s.distances(queries)
         if count_edges:
             r.edges = s.run(queries, count_edges=True).edges
         return r
+
+
+def path_to_set(parent_row: np.ndarray, v: int) -> list:
+    """The shortest path [v, ..., source] from v to its group, read off one row of a parent
+    matrix (BfsResult.parent[k]); [] if v is unreached. Its length is dist[k, v] + 1."""
+    parent_row = np.asarray(parent_row)
+    v = int(v)
+    if not 0 <= v < len(parent_row) or parent_row[v] < 0:
+        return []
+    path = [v]
+    while int(parent_row[v]) != v:
+        v = int(parent_row[v])
+        path.append(v)
+        if len(path) > len(parent_row):
+            raise ValueError("parent_row has a cycle: not a BFS parent array")
+    return path
+
+
+def nearest_source(parent: np.ndarray) -> np.ndarray:
+    """int32[K, n]: the source each vertex's parent path ends at (the member of the group it is
+    nearest to under the first-in-row rule; the graph Voronoi partition), -1 where unreached.
+    Pointer doubling: ceil(log2(longest path)) numpy passes over the matrix."""
+    P = np.array(parent, dtype=np.int32, ndmin=2)
+    K, n = P.shape
+    reached = P >= 0
+    cur = np.where(reached, P, np.arange(n, dtype=np.int32)[None, :])
+    rows = np.arange(K)[:, None]
+    for _ in range(max(1, int(n).bit_length())):
+        nxt = cur[rows, cur]
+        if np.array_equal(nxt, cur):
+            break
+        cur = nxt
+    out = np.where(reached, cur, -1).astype(np.int32)
+    return out if np.ndim(parent) == 2 else out[0]
 
 
 def argmin_first(F: np.ndarray) -> int:

@@ -115,6 +115,13 @@ def _sig(lib):
                                                  P(Stats), vp]),
         "msbfs_cpu_run_dist": (C.c_int, [C.c_int64, i64p, i32p, C.c_int64, i64p, i32p, i64p, i32p,
                                          C.c_int64, C.c_int]),
+        "msbfs_solver_run_parents": (C.c_int, [vp, C.c_int64, i64p, i32p, i64p, vp, vp, C.c_int64,
+                                               P(Stats), vp]),
+        "msbfs_solver_run_parents_host": (C.c_int, [vp, C.c_int64, i64p, i32p, i64p, i32p, i32p,
+                                                    C.c_int64, P(Stats), vp]),
+        "msbfs_parents_wide_degree": (C.c_int, []),
+        "msbfs_cpu_run_parents": (C.c_int, [C.c_int64, i64p, i32p, C.c_int64, i64p, i32p, i64p,
+                                            i32p, i32p, C.c_int64, C.c_int]),
         "msbfs_solver_free": (None, [vp]),
         "msbfs_solver_levels": (C.c_int64, [vp, P(Level), C.c_int64]),
         "msbfs_argmin": (C.c_int64, [i64p, C.c_int64]),
