@@ -98,6 +98,7 @@ struct RunStats {
   int64_t levels = 0, td_levels = 0, bu_levels = 0, batches = 0;
   double device_ms = 0;
   int64_t builds = 0;  // query-dependent tables built by the run itself (see prepare_queries)
+  int64_t leaf_folded = 0;  // degree-1 vertices the run kept out of its traversal (0: unfolded)
   std::vector<LevelRec> recs;
 };
 

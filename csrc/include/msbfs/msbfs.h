@@ -33,6 +33,9 @@ typedef struct {
   /* tables the run had to build itself (bit-parallel: prefix lengths for a bound that
    * msbfs_solver_prepare / _prepare_queries did not build); 0 after a matching prepare */
   int64_t builds;
+  /* bit-parallel: degree-1 vertices kept out of the traversal and counted through their only
+   * neighbour (tuning key leaf); 0 for an unfolded run */
+  int64_t leaf_folded;
 } msbfs_stats;
 
 /* one BFS level of the last run (bit-parallel solver): direction 'T' (top-down push) or 'B'
@@ -214,6 +217,16 @@ void msbfs_solver_free(msbfs_solver s);
  *             rank r, in rank order), all-reduce SUM of out -> reduced
  *   C: phase_c(recv, reduced) -> F_local[64*nwords] (levels >= 3 of the own groups)
  *   F[k] = reduced[k] + F_local[k - 64*wbeg[rank]] for the own groups. */
+/* Leaf folding of the bit-parallel solver (tuning key leaf; kernels/bitpar/leaf.hpp), host code
+ * only. _on: is a run folded (leaf_key: 0 off, 1 on where legal, -1 auto)? _lists: the tables of
+ * a host CSR with sorted rows and degrees non-increasing in the id: info[8] = n_core, n_eff,
+ * parents, attached leaves, largest weight, padded small-class positions, heavy parents, list
+ * positions; leafw[n_core], pidx[n_core], plist / pw[cap >= positions] where not NULL. */
+int msbfs_leaf_fold_on(int leaf_key, int relabelled, int rows_sorted, int count, int nparts,
+                       int limited, int64_t n_core, int64_t n_eff);
+int msbfs_leaf_fold_lists(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t* info,
+                          int32_t* leafw, int64_t cap, int32_t* plist, int32_t* pw,
+                          int32_t* pidx);
 int msbfs_hybrid_extent(msbfs_graph g, int64_t* n_eff);
 int64_t msbfs_solver_hybrid_max_groups(msbfs_solver s);
 int msbfs_solver_hybrid_phase_a(msbfs_solver s, int64_t K, const int64_t* qoff,

@@ -55,13 +55,17 @@ void Tuning::set(const std::string& key, const std::string& v) {
     tiles_w = (int)to_num(key, v);
     if (tiles_w != 4 && tiles_w != 8 && tiles_w != 16) fail("tuning: tiles_w must be 4, 8 or 16");
   }
+  else if (key == "leaf") {
+    leaf = (int)to_num(key, v);
+    if (leaf < -1 || leaf > 1) fail("tuning: leaf must be 0 (off), 1 (on where legal) or -1 (auto)");
+  }
   else if (key == "dirs") {
     for (char c : v)
       if (c != 'T' && c != 'B' && c != '.') fail("tuning: dirs takes T, B or . per level");
     dirs = v;
   } else {
     fail("tuning: unknown key '" + key +
-         "' (gamma gamma2 pfx codes code_deg lean lean_min lazy td_fused td_bm batch bu_max tiles tiles_code_deg full dskip push_after dskip3 chunk2 wide_few pfx_h filter_frac tiles_w dirs)");
+         "' (gamma gamma2 pfx codes code_deg lean lean_min lazy td_fused td_bm batch bu_max tiles tiles_code_deg full dskip push_after dskip3 chunk2 wide_few pfx_h filter_frac tiles_w leaf dirs)");
   }
 }
 

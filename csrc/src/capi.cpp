@@ -10,6 +10,7 @@
 #include "msbfs/dist_stage.hpp"
 #include "msbfs/graph.hpp"
 #include "msbfs/msbfs.h"
+#include "kernels/bitpar/leaf.hpp"
 
 struct msbfs_graph_s {
   msbfs::DeviceGraph g;
@@ -85,6 +86,7 @@ void timed(msbfs_solver s, void* stream, msbfs_stats* st, const char* what, Fn&&
     st->batches = rs.batches;
     st->device_ms = ms;
     st->builds = rs.builds;
+    st->leaf_folded = rs.leaf_folded;
   }
 }
 
@@ -591,6 +593,45 @@ int msbfs_cpu_run_parents(int64_t n, const int64_t* rowptr, const int32_t* col, 
     std::vector<int64_t> f;
     msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, dist, ld, parent);
     std::memcpy(F, f.data(), K * sizeof(int64_t));
+  });
+}
+
+int msbfs_leaf_fold_on(int leaf_key, int relabelled, int rows_sorted, int count, int nparts,
+                       int limited, int64_t n_core, int64_t n_eff) {
+  msbfs::bp::LeafRun r;
+  r.leaf_key = leaf_key;
+  r.relabelled = relabelled != 0;
+  r.rows_sorted = rows_sorted != 0;
+  r.count = count != 0;
+  r.nparts = nparts;
+  r.limited = limited != 0;
+  return msbfs::bp::leaf_fold_on(r, n_core, n_eff) ? 1 : 0;
+}
+
+int msbfs_leaf_fold_lists(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t* info,
+                          int32_t* leafw, int64_t cap, int32_t* plist, int32_t* pw,
+                          int32_t* pidx) {
+  return guard([&] {
+    namespace bp = msbfs::bp;
+    if (n < 0 || n > INT32_MAX) msbfs::fail("leaf_fold_lists: n out of range");
+    for (int64_t v = 0; v + 1 < n; ++v)
+      if (rowptr[v + 2] - rowptr[v + 1] > rowptr[v + 1] - rowptr[v])
+        msbfs::fail("leaf_fold_lists: degrees must be non-increasing in the id");
+    const int64_t n_core = bp::first_below_degree(rowptr, n, 2);
+    const int64_t n_eff = bp::first_below_degree(rowptr, n, 1);
+    std::vector<int32_t> w((size_t)std::max<int64_t>(n_core, 1), 0);
+    bp::leaf_weights_host(rowptr, col, n_core, w.data());
+    const bp::LeafLists L = bp::build_leaf_lists(w.data(), n_core, n_eff);
+    const int64_t out[8] = {L.n_core, L.n_eff,  L.parents, L.attached,
+                            L.max_w,  L.nsmall, L.nheavy,  L.positions()};
+    std::copy(out, out + 8, info);
+    if (leafw) std::copy(w.begin(), w.begin() + n_core, leafw);
+    if (plist || pw) {
+      if (cap < L.positions()) msbfs::fail("leaf_fold_lists: list buffers too small");
+      if (plist) std::copy(L.plist.begin(), L.plist.begin() + L.positions(), plist);
+      if (pw) std::copy(L.pw.begin(), L.pw.begin() + L.positions(), pw);
+    }
+    if (pidx) std::copy(L.pidx.begin(), L.pidx.begin() + n_core, pidx);
   });
 }
 

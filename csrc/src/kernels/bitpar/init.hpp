@@ -61,7 +61,8 @@ __global__ __launch_bounds__(kBlock) void k_init(const int32_t* pv, const int32_
                                                  uint64_t* visB, uint64_t* acc, int32_t* stamp,
                                                  int32_t epoch, int32_t* fl, Ctr* ctr,
                                                  unsigned long long* E, uint64_t* alive,
-                                                 uint32_t* anyvis, const int32_t* relabel) {
+                                                 uint32_t* anyvis, const int32_t* relabel,
+                                                 uint8_t* first = nullptr) {
   __shared__ LdsQueue q;
   __shared__ unsigned long long scratch[kWaves];
   q_init(q);
@@ -78,6 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_init(const int32_t* pv, const int32_
       const int word = k >> 6;
       const uint64_t bit = 1ull << (k & 63);
       const uint64_t old = atomicOr((unsigned long long*)&visA[(int64_t)v * W + word], bit);
+      if (first) first[i] = !(old & bit);  // (leaf folding: the pair's first occurrence)
       if (!(old & bit)) {
         atomicOr((unsigned long long*)&visB[(int64_t)v * W + word], bit);
         atomicOr((unsigned long long*)&acc[(int64_t)v * W + word], bit);

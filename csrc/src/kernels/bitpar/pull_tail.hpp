@@ -82,7 +82,8 @@ template <int W>
 __global__ __launch_bounds__(kBlock) void k_push_tail(
     const int32_t* fl, int64_t nf, int32_t H, const int64_t* rowptr, const int32_t* col,
     const uint64_t* R, const uint32_t* code, int32_t code_from, const uint32_t* done,
-    int part, int nparts, uint64_t* acc, int32_t* stamp, int32_t epoch, int split) {
+    int part, int nparts, uint64_t* acc, int32_t* stamp, int32_t epoch, int split,
+    int32_t vmax = INT32_MAX) {
   constexpr int PG = 64;  // lanes per wave: an entry's lanes take consecutive row entries
   // `split` waves per frontier entry (wave s of entry i takes row entries s*64 + lane, step
   // split*64; the host splits small frontiers only), UN entries per lane in flight: a frontier
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_push_tail(
         const int64_t k = k0 + q * kStep;
         const int32_t x = col[k < e ? k : k0];
         v[q] = x;
-        ok[q] = k < e;
+        ok[q] = k < e && x < vmax;  // (vmax: leaf folding pushes to no id >= n_core)
       }
 #pragma unroll
       for (int q = 0; q < UN; ++q)
@@ -164,7 +165,7 @@ template <int W>
 __global__ __launch_bounds__(kBlock) void k_push_tail_after(
     const int32_t* fl, int64_t nf, int32_t H, const int64_t* rowptr, const int32_t* col,
     const uint64_t* R, const uint32_t* code, int32_t code_from, uint64_t* O, uint32_t* fbm,
-    uint32_t* anyvis, Ctr* ctr, uint32_t* slabF) {
+    uint32_t* anyvis, Ctr* ctr, uint32_t* slabF, int32_t vmax = INT32_MAX) {
   __shared__ uint32_t cnt[64 * W];
   __shared__ unsigned long long scratch[kWaves];
   __shared__ uint32_t scratch32[kWaves];
@@ -183,6 +184,7 @@ __global__ __launch_bounds__(kBlock) void k_push_tail_after(
     const int64_t b = rowptr[u], e = rowptr[u + 1];
     for (int64_t k = b + lane; k < e; k += 64) {
       const int32_t v = col[k];
+      if (v >= vmax) continue;  // (leaf folding: an id >= n_core has no output row)
       // (every target has its output row: the tiles and the big vertices' finalize write one
       // for the vertices done before this level too, holding every alive group)
       bool added = false;

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(kBlock) void k_td_expand(
     const int32_t* fl, int64_t nf, const int64_t* offs, const int64_t* rowptr, const int32_t* col,
     const uint64_t* visCur, const uint64_t* fsrc, const uint32_t* done, uint64_t* accNext,
     int32_t* stamp, int32_t epoch, int32_t* touched, Ctr* ctr, const uint32_t* lzv = nullptr,
-    const uint32_t* osnap = nullptr) {
+    const uint32_t* osnap = nullptr, int32_t vmax = INT32_MAX) {
   using L = Lay<W>;
   constexpr int VW = L::VW, G = L::G, VPW = L::VPW, TILE = L::TILE;
   __shared__ LdsQueue q;
@@ -36,7 +36,8 @@ __global__ __launch_bounds__(kBlock) void k_td_expand(
       const int32_t u = fl[i];
       const int64_t start = i ? offs[i - 1] : 0;
       v = col[rowptr[u] + (e - start)];
-      if (!is_done(done, v)) {
+      // (vmax: leaf folding pushes to no id >= n_core, see bitpar/leaf.hpp)
+      if (v < vmax && !is_done(done, v)) {
         const int64_t uo = (int64_t)u * W + slot * VW, vo = (int64_t)v * W + slot * VW;
         V<VW> fb = ldv<VW>(visCur + uo);
         if constexpr (DIFF) {
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void k_td_expand_small(
     const int32_t* col, const uint64_t* visCur, const uint64_t* fsrc, const uint32_t* done,
     uint64_t* accNext, int32_t* stamp, int32_t epoch, int32_t* touched, Ctr* ctr,
     const uint32_t* lzv = nullptr, const uint32_t* osnap = nullptr, Ctr* cstop = nullptr,
-    unsigned long long ef_stop = 0) {
+    unsigned long long ef_stop = 0, int32_t vmax = INT32_MAX) {
   using L = Lay<W>;
   constexpr int VW = L::VW, G = L::G, VPW = L::VPW, TILE = L::TILE;
   // device-driven batch: stop where the host would pull (cstop = the slot of this level's
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void k_td_expand_small(
       int32_t v = 0;
       if (e < end) {
         v = col[e];
-        if (!is_done(done, v)) {
+        if (v < vmax && !is_done(done, v)) {
           const int64_t vo = (int64_t)v * W + slot * VW;
           const V<VW> r = (lzv && !any_visited(lzv, v)) ? vzero<VW>() : ldv<VW>(visCur + vo);
           bool any = false, first = false;
@@ -287,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void k_td_fused(
     uint64_t* accCur, uint64_t* accNext, const uint64_t* alive, const uint64_t* gmask,
     uint32_t* done, uint32_t* anyvis, int32_t* stamp, int32_t epoch, int32_t* flNext, Ctr* ctr,
     uint32_t* slabF, Ctr* cprev, int own, int tail, const Ctr* cpp,
-    unsigned long long ef_stop) {
+    unsigned long long ef_stop, int32_t vmax = INT32_MAX) {
   using L = Lay<W>;
   constexpr int VW = L::VW, G = L::G, VPW = L::VPW, TILE = L::TILE;
   constexpr int U = 4;
@@ -348,7 +349,10 @@ __global__ __launch_bounds__(kBlock) void k_td_fused(
       uint32_t dw[U];
       V<VW> r[U];
 #pragma unroll
-      for (int j = 0; j < U; ++j) v[j] = e + j < end ? col[e + j] : -1;
+      for (int j = 0; j < U; ++j) {
+        v[j] = e + j < end ? col[e + j] : -1;
+        if (v[j] >= vmax) v[j] = -1;  // (leaf folding: no push to an id >= n_core)
+      }
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         dw[j] = ~0u;

@@ -39,6 +39,8 @@
 //   bitpar_pull.hip    bottom-up levels (prefix pull + tail push, narrow / lean / chunk pulls),
 //                      each carried out from a plan: bitpar/pull_plan.hpp (plain host code)
 //   bitpar_tiles.hip   the first pull level over static vertex tiles
+//   bitpar/leaf.hpp  leaf_kernels.hpp    leaf folding: degree-1 vertices counted through their parents
+//                                        (decision and lists: plain host code; launched from bitpar_pull.hip)
 //   bitpar/tuning.hpp, ../bitpar_tuning.cpp   the tuning keys and their parser (plain host code)
 //   bitpar_hybrid.hip  the hybrid multi-GPU phases and the exchange coding
 #pragma once
@@ -50,6 +52,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "leaf.hpp"
 #include "pull_plan.hpp"
 #include "record.hpp"
 
@@ -152,6 +155,7 @@ class BitparSolver final : public Solver {
     // at the start of the first pull level after each skipping level)
     bool skipped_any = false, resnap = false;
     char kind = 0;  // the last pull level's PullPlan::kind (its level record's)
+    bool fold = false;  // leaf folding (bitpar/leaf.hpp): the traversal ends at leaf_.n_core
   };
   struct Small {
     unsigned long long* F;
@@ -282,6 +286,7 @@ class BitparSolver final : public Solver {
   struct TileSet {
     DevBuf pent, tiles, big;
     int64_t ntiles = 0, nbig = 0, nent = 0;
+    int64_t t_core = 0;  // tiles of the ids < leaf_n_core() (a tile ends there; part 0 of 1)
     std::vector<int64_t> ti, te;  // host: own-vertex index and first entry of every tile (+ end)
     int64_t last_partial = -1;    // last tile of a big vertex (they all precede chunk 1)
     int part = -1, nparts = 0;
@@ -347,6 +352,43 @@ class BitparSolver final : public Solver {
     const double mean = (double)g_.nnz / (double)std::max<int64_t>(n_eff(), 1);
     return (double)g_.max_degree > 16.0 * mean ? tun_.gamma2 : tun_.gamma;
   }
+
+  // ---- leaf folding (bitpar/leaf.hpp; bitpar_pull.hip)
+  struct LeafState {
+    const void* key[3] = {nullptr, nullptr, nullptr};  // the graph buffers the tables are for
+    bool bounds = false, lists = false;                // n_core known / the lists are built
+    bool no_room = false;                              // ... or did not fit: runs stay unfolded
+    int64_t n_core = 0, parents = 0, attached = 0, max_w = 0, nsmall = 0, nheavy = 0;
+    DevBuf plist, pw, pidx, seen, epoch, first;
+    // Leaf rows are written by k_init alone while folding, so in both visited buffers they must be
+    // all zero or the batch's source bits: a folded batch zeroes its source rows again at its
+    // end, and the first one after anything else (an unfolded batch, another word count) zeroes
+    // the whole leaf range.
+    bool rows_dirty = true;
+    int rows_w = 0;
+  };
+  LeafState leaf_;
+  int32_t leaf_epoch_ = 0;
+  // first id of degree <= 1 (n_eff() where the ids are not in degree order)
+  int64_t leaf_n_core();
+  // is this run folded? builds the lists on first use (prepare() does it before any timed run)
+  bool leaf_fold_for(bool count, int nparts, bool limited, hipStream_t s);
+  void leaf_build(hipStream_t s);
+  template <int W>
+  void leaf_begin(Loop& S, hipStream_t s);  // before start_batch
+  template <int W>
+  void leaf_sources(const int32_t* pv, const int32_t* pk, int64_t np, hipStream_t s);
+  template <int W>
+  void leaf_end(const int32_t* pv, int64_t np, hipStream_t s);
+  // The weighted count of one level (weight = level + 1) after its kernels: R = the buffer the
+  // level wrote, alive = the mask its kernels used. The new frontier's list (n entries, or *n_dev)
+  // where that is short, else (list == nullptr) every parent.
+  template <int W>
+  void leaf_weigh(const uint64_t* R, const uint64_t* alive, uint32_t weight, const int32_t* list,
+                  int64_t n, const uint32_t* n_dev, hipStream_t s);
+  // vertices a folded run's traversal covers (else every non-isolated one)
+  int64_t extent(const Loop& S) { return S.fold ? leaf_.n_core : n_eff(); }
+  int32_t push_bound(const Loop& S) const { return S.fold ? (int32_t)leaf_.n_core : INT32_MAX; }
 
   // 1 + the last vertex with deg > 0 (cached per graph buffers: relabelling replaces them).
   // Vertices beyond it are never active, never neighbours: level loops and clears skip them.

@@ -77,6 +77,10 @@ struct Tuning {
   // row gather), so rows with up to ~12 expected bits are worth a try (RMAT-26 level 2: 3 ->
   // 12: 13.85 -> 13.32 ms)
   double tiles_code_deg = 12.0;
+  // leaf folding (bitpar/leaf.hpp): the degree-1 vertices of a degree-relabelled graph stay out
+  // of a plain F run's traversal and are counted through their parents. 0 off, 1 on wherever it
+  // is legal, -1 (default) on where leaves are at least 1/8 of the non-isolated vertices
+  int leaf = -1;
   std::string dirs;    // forced per-level directions 'T'/'B' (tests, experiments)
 
   void set(const std::string& key, const std::string& value);

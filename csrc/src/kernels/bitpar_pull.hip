@@ -2,8 +2,11 @@
 // pull + tail push on the first pull level, narrow / lean / hub-chunk pulls after it
 // (level_bu). Design overview: bitpar/solver.hpp; kernels: bitpar/pull.hpp.
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 
 #include "bitpar/init.hpp"
+#include "bitpar/leaf_kernels.hpp"
 #include "bitpar/pull.hpp"
 #include "bitpar/pull_full.hpp"
 #include "bitpar/solver.hpp"
@@ -109,6 +112,7 @@ void BitparSolver::prepare(hipStream_t s) {
     if (tiles_possible()) (void)pfx_tiles(maxW_, 0, 1, s);  // (the first pull level's tiles)
   }
   if (tun_.lean) first_nbr(s);
+  (void)leaf_fold_for(false, 1, false, s);  // (the parent lists of leaf folding, where it applies)
   if (tun_.dskip) dsnap_.ensure(std::max<size_t>((size_t)((g_.n + 31) / 32) * sizeof(uint32_t), 4));
   (void)code_bound(1.0);
   DevBuf c;
@@ -146,6 +150,7 @@ void BitparSolver::prepare_queries(int64_t K, const int64_t* qoff, const int32_t
     const size_t hbytes = 32 * sizeof(uint64_t) + (size_t)np_max * 2 * sizeof(int32_t);
     if (!hsrc_ || hsrc_->bytes < hbytes) hsrc_ = std::make_unique<PinnedBuf>(hbytes + hbytes / 2);
     pairs_.ensure((size_t)np_max * 2 * sizeof(int32_t));
+    leaf_.first.ensure((size_t)np_max);
   }
   if (!prefix_capable(plan_graph(), tun_)) {
     MSBFS_HIP_CHECK(hipStreamSynchronize(s));
@@ -305,7 +310,7 @@ void BitparSolver::bu_tail_push(Loop& S, BuLevel& L, hipStream_t s) {
   k_push_tail<W><<<grid_for(S.nf * 64 * split, kBlock, 8192), kBlock, 0, s>>>(
       fl_[S.fc].as<int32_t>(), S.nf, L.H, g_.rowptr, g_.col, L.R, L.codes, L.code_from,
       p.tiled ? nullptr : done_.as<uint32_t>(), S.part, S.nparts, acc_[S.ac].as<uint64_t>(),
-      (p.tiled || p.pfx_nostamp) ? nullptr : stamp_.as<int32_t>(), epoch_, split);
+      (p.tiled || p.pfx_nostamp) ? nullptr : stamp_.as<int32_t>(), epoch_, split, push_bound(S));
   MSBFS_HIP_CHECK(hipGetLastError());
 }
 
@@ -323,7 +328,8 @@ void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
       if (L.rows + gp > 3 * kMaxGrid) fail("tail push: counter slab rows exhausted");
       k_push_tail_after<W><<<gp, kBlock, 0, s>>>(
           fl_[S.fc].as<int32_t>(), S.nf, kPfxH, g_.rowptr, g_.col, L.R, L.codes, L.code_from, L.O,
-          fbm_tile_.as<uint32_t>(), anyvis_.as<uint32_t>(), ctr_.as<Ctr>(), slabF<W>(L.rows));
+          fbm_tile_.as<uint32_t>(), anyvis_.as<uint32_t>(), ctr_.as<Ctr>(), slabF<W>(L.rows),
+          push_bound(S));
       MSBFS_HIP_CHECK(hipGetLastError());
       L.rows += gp;
       S.push_after = false;
@@ -600,6 +606,8 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
                                                        sm.E, aslot + 16 * (i + 1), level0 + 1 + i,
                                                        gate);
     MSBFS_HIP_CHECK(hipGetLastError());
+    // (a closed level appends nothing: its list is empty)
+    if (S.fold) leaf_weigh<W>(O, alive, level0 + 2 + i, fl_out, 0, &slots[i + 1].fl2.v, s);
   }
   MSBFS_HIP_CHECK(hipMemcpyAsync(hbctr_->p, bctr_.p, (size_t)(K + 1) * sizeof(Ctr),
                                  hipMemcpyDeviceToHost, s));
@@ -654,7 +662,167 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
   bu_next_ = real == K ? std::min(2 * K, kBatch) : real + 1;
 }
 
+
+// ---- leaf folding (bitpar/leaf.hpp) -------------------------------------------------------------
+int64_t BitparSolver::leaf_n_core() {
+  if (leaf_.key[0] != (const void*)g_.rowptr || leaf_.key[1] != (const void*)g_.col ||
+      leaf_.key[2] != (const void*)g_.old2new) {
+    leaf_ = LeafState{};
+    leaf_.key[0] = g_.rowptr;
+    leaf_.key[1] = g_.col;
+    leaf_.key[2] = g_.old2new;
+  }
+  if (!leaf_.bounds) {
+    const int64_t ne = n_eff();
+    // (the first id of degree < 2; the table is empty for ids that are not in degree order)
+    leaf_.n_core = (g_.old2new && g_.rows_sorted && g_.n <= INT32_MAX)
+                       ? std::min<int64_t>(code_bound(2.0), ne)
+                       : ne;
+    leaf_.bounds = true;
+  }
+  return leaf_.n_core;
+}
+
+bool BitparSolver::leaf_fold_for(bool count, int nparts, bool limited, hipStream_t s) {
+  if (tun_.leaf == 0) return false;
+  LeafRun r;
+  r.leaf_key = tun_.leaf;
+  r.relabelled = g_.old2new != nullptr;
+  r.rows_sorted = g_.rows_sorted;
+  r.count = count;
+  r.nparts = nparts;
+  r.limited = limited;
+  if (!r.relabelled || !r.rows_sorted) return false;
+  if (!leaf_fold_on(r, leaf_n_core(), n_eff())) return false;
+  if (!leaf_.lists && !leaf_.no_room) leaf_build(s);
+  return leaf_.lists;
+}
+
+// the parents' weights (device), their lists (host, bitpar/leaf.hpp) and the count's own record
+void BitparSolver::leaf_build(hipStream_t s) {
+  const int64_t nc = leaf_n_core(), ne = n_eff();
+  DevBuf lw((size_t)std::max<int64_t>(nc, 1) * sizeof(int32_t));
+  std::vector<int32_t> hw((size_t)std::max<int64_t>(nc, 1), 0);
+  if (nc > 0) {
+    k_leaf_weights<<<grid_for(nc, kBlock, 8192), kBlock, 0, s>>>(g_.rowptr, g_.col, nc,
+                                                                  lw.as<int32_t>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+    MSBFS_HIP_CHECK(hipMemcpyAsync(hw.data(), lw.p, (size_t)nc * sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, s));
+  }
+  MSBFS_HIP_CHECK(hipStreamSynchronize(s));
+  const LeafLists L = build_leaf_lists(hw.data(), nc, ne);
+  const size_t np = (size_t)std::max<int64_t>(L.positions(), 1);
+  const size_t need = np * (8 + (size_t)maxW_ * sizeof(uint64_t)) + L.pidx.size() * 4;
+  size_t fr = 0, tot = 0;
+  MSBFS_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if (need + ((size_t)2 << 30) > fr && need > ((size_t)64 << 20)) {  // (no room: unfolded)
+    leaf_.no_room = true;
+    return;
+  }
+  leaf_.plist.alloc(np * sizeof(int32_t));
+  leaf_.pw.alloc(np * sizeof(int32_t));
+  leaf_.pidx.alloc(L.pidx.size() * sizeof(int32_t));
+  leaf_.seen.alloc(np * (size_t)maxW_ * sizeof(uint64_t));
+  leaf_.epoch.alloc(np * sizeof(int32_t));
+  leaf_.first.ensure((size_t)1 << 16);
+  MSBFS_HIP_CHECK(hipMemcpyAsync(leaf_.plist.p, L.plist.data(), np * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, s));
+  MSBFS_HIP_CHECK(hipMemcpyAsync(leaf_.pw.p, L.pw.data(), np * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, s));
+  MSBFS_HIP_CHECK(hipMemcpyAsync(leaf_.pidx.p, L.pidx.data(), L.pidx.size() * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, s));
+  MSBFS_HIP_CHECK(hipMemsetAsync(leaf_.epoch.p, 0, np * sizeof(int32_t), s));
+  MSBFS_HIP_CHECK(hipStreamSynchronize(s));  // (L is a host object)
+  leaf_epoch_ = 0;
+  leaf_.parents = L.parents;
+  leaf_.attached = L.attached;
+  leaf_.max_w = L.max_w;
+  leaf_.nsmall = L.nsmall;
+  leaf_.nheavy = L.nheavy;
+  leaf_.rows_dirty = true;
+  leaf_.lists = true;
+  if (getenv("MSBFS_TRACE"))
+    fprintf(stderr,
+            "[msbfs bp] leaf folding: n_core=%lld n_eff=%lld leaves=%lld (attached %lld) "
+            "parents=%lld (heavy %lld) max leafw=%lld\n",
+            (long long)nc, (long long)ne, (long long)(ne - nc), (long long)L.attached,
+            (long long)L.parents, (long long)L.nheavy, (long long)L.max_w);
+}
+
+template <int W>
+void BitparSolver::leaf_begin(Loop& S, hipStream_t s) {
+  (void)S;
+  if (++leaf_epoch_ == INT32_MAX) {  // (epoch 0 = never written)
+    MSBFS_HIP_CHECK(hipMemsetAsync(leaf_.epoch.p, 0, leaf_.epoch.bytes, s));
+    leaf_epoch_ = 1;
+  }
+  if (leaf_.rows_dirty || leaf_.rows_w != W) {
+    const size_t off = (size_t)leaf_.n_core * W * sizeof(uint64_t);
+    const size_t len = (size_t)(n_eff() - leaf_.n_core) * W * sizeof(uint64_t);
+    for (int i = 0; i < 2; ++i)
+      MSBFS_HIP_CHECK(hipMemsetAsync((char*)vis_[i].p + off, 0, len, s));
+  }
+  leaf_.rows_dirty = true;  // (until leaf_end has cleared this batch's source rows)
+  leaf_.rows_w = W;
+}
+
+template <int W>
+void BitparSolver::leaf_end(const int32_t* pv, int64_t np, hipStream_t s) {
+  if (np > 0) {
+    k_zero_src_rows<W><<<grid_for(np * W, kBlock), kBlock, 0, s>>>(
+        pv, np, g_.old2new, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+  }
+  leaf_.rows_dirty = false;
+}
+
+template <int W>
+void BitparSolver::leaf_sources(const int32_t* pv, const int32_t* pk, int64_t np, hipStream_t s) {
+  const Small sm = small();
+  k_leaf_sources<W><<<grid_for(np, kBlock), kBlock, 0, s>>>(
+      pv, pk, leaf_.first.as<uint8_t>(), np, g_.old2new, g_.rowptr, g_.col,
+      vis_[0].as<uint64_t>(), anyvis_.as<uint32_t>(), (int32_t)leaf_.n_core, (int32_t)n_eff(),
+      sm.F);
+  MSBFS_HIP_CHECK(hipGetLastError());
+  // level 0: the parents among the sources (the first frontier list; its length is ctr's fl2)
+  leaf_weigh<W>(vis_[0].as<uint64_t>(), sm.alive[0], 1, fl_[0].as<int32_t>(), 0,
+                &ctr_.as<Ctr>()->fl2.v, s);
+}
+
+template <int W>
+void BitparSolver::leaf_weigh(const uint64_t* R, const uint64_t* alive, uint32_t weight,
+                              const int32_t* list, int64_t n, const uint32_t* n_dev,
+                              hipStream_t s) {
+  using L = Lay<W>;
+  const Small sm = small();
+  const LeafArgs a{leaf_.plist.as<int32_t>(), leaf_.pw.as<int32_t>(), leaf_.pidx.as<int32_t>(),
+                   leaf_.seen.as<uint64_t>(), leaf_.epoch.as<int32_t>(), leaf_epoch_, R,
+                   anyvis_.as<uint32_t>(), done_.as<uint32_t>(), alive, sm.gmask, sm.F, weight};
+  if (list) {
+    // (a device-side length: these are the short lists of the late levels and the batches)
+    const int g = n_dev ? 64 : grid_for(n, kLeafU * L::TILE, 1024);
+    if (!n_dev && n <= 0) return;
+    k_leaf_weigh_list<W><<<g, kBlock, 0, s>>>(a, list, n, n_dev, 0, (int32_t)leaf_.n_core);
+  } else {
+    if (leaf_.nsmall > 0)
+      k_leaf_weigh<W><<<grid_for(leaf_.nsmall, kLeafU * L::TILE, 8 * std::max(1, num_cus())),
+                        kBlock, 0, s>>>(a, leaf_.nsmall);
+    if (leaf_.nheavy > 0)
+      k_leaf_weigh_list<W><<<grid_for(leaf_.nheavy, kLeafU * L::TILE, 1024), kBlock, 0, s>>>(
+          a, nullptr, leaf_.nheavy, nullptr, leaf_.nsmall, (int32_t)leaf_.n_core);
+  }
+  MSBFS_HIP_CHECK(hipGetLastError());
+}
+
 #define MSBFS_BP_INST(WW)                                                 \
+  template void BitparSolver::leaf_begin<WW>(Loop&, hipStream_t);        \
+  template void BitparSolver::leaf_end<WW>(const int32_t*, int64_t, hipStream_t);                 \
+  template void BitparSolver::leaf_sources<WW>(const int32_t*, const int32_t*, int64_t,           \
+                                               hipStream_t);                                      \
+  template void BitparSolver::leaf_weigh<WW>(const uint64_t*, const uint64_t*, uint32_t,          \
+                                             const int32_t*, int64_t, const uint32_t*,            \
+                                             hipStream_t);                                        \
   template void BitparSolver::fix_done_rows<WW>(Loop&, hipStream_t);     \
   template int BitparSolver::level_bu<WW, false>(Loop&, hipStream_t);    \
   template int BitparSolver::level_bu<WW, true>(Loop&, hipStream_t);     \

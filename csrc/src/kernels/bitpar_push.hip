@@ -21,6 +21,7 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
   const uint64_t* alive = sm.alive[S.alv];
   ++epoch_;
   const uint32_t* lzv = S.lazy ? anyvis_.as<uint32_t>() : nullptr;  // see k_zero_part_rows
+  const int32_t vmax = push_bound(S);  // (leaf folding: no push to an id >= n_core)
   if (g_.max_degree <= kSmallDeg) {
     // low-degree graph: vertex-parallel expansion, no degree scan
     const int eg = grid_for(S.nf, L::TILE, 4096);
@@ -29,14 +30,14 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
           fl_[S.fc].as<int32_t>(), S.nf, nullptr, g_.rowptr, g_.col, R,
           acc_[S.ac].as<uint64_t>(),
           done_.as<uint32_t>(), acc_[S.ac ^ 1].as<uint64_t>(), stamp_.as<int32_t>(), epoch_,
-          touched_.as<int32_t>(), ctr_.as<Ctr>(), lzv);
+          touched_.as<int32_t>(), ctr_.as<Ctr>(), lzv, nullptr, nullptr, 0, vmax);
     else
       k_td_expand_small<W, true><<<eg, kBlock, 0, s>>>(
           fl_[S.fc].as<int32_t>(), S.nf, nullptr, g_.rowptr, g_.col, R, O,
           done_.as<uint32_t>(),
           acc_[S.ac ^ 1].as<uint64_t>(), stamp_.as<int32_t>(), epoch_,
           touched_.as<int32_t>(), ctr_.as<Ctr>(), lzv,
-          S.osnap_next ? asnap_.as<uint32_t>() : nullptr);
+          S.osnap_next ? asnap_.as<uint32_t>() : nullptr, nullptr, 0, vmax);
   } else {
   frontier_degree_scan(g_.rowptr, fl_[S.fc].as<int32_t>(), S.nf, offs_.as<int64_t>(),
                        scan_tmp_.p, scan_bytes_, s);
@@ -45,13 +46,13 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
     k_td_expand<W, false><<<eg, kBlock, 0, s>>>(
         fl_[S.fc].as<int32_t>(), S.nf, offs_.as<int64_t>(), g_.rowptr, g_.col, R,
         acc_[S.ac].as<uint64_t>(), done_.as<uint32_t>(), acc_[S.ac ^ 1].as<uint64_t>(),
-        stamp_.as<int32_t>(), epoch_, touched_.as<int32_t>(), ctr_.as<Ctr>(), lzv);
+        stamp_.as<int32_t>(), epoch_, touched_.as<int32_t>(), ctr_.as<Ctr>(), lzv, nullptr, vmax);
   else
     k_td_expand<W, true><<<eg, kBlock, 0, s>>>(
         fl_[S.fc].as<int32_t>(), S.nf, offs_.as<int64_t>(), g_.rowptr, g_.col, R, O,
         done_.as<uint32_t>(), acc_[S.ac ^ 1].as<uint64_t>(), stamp_.as<int32_t>(), epoch_,
         touched_.as<int32_t>(), ctr_.as<Ctr>(), lzv,
-        S.osnap_next ? asnap_.as<uint32_t>() : nullptr);
+        S.osnap_next ? asnap_.as<uint32_t>() : nullptr, vmax);
   }
   MSBFS_HIP_CHECK(hipGetLastError());
   // touched <= min(n, frontier edges); the kernel reads the exact count from ctr
@@ -126,6 +127,7 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
   uint64_t* R = vis_[S.cur].as<uint64_t>();
   uint64_t* O = vis_[S.cur ^ 1].as<uint64_t>();
   const uint32_t level0 = S.level;
+  const int32_t vmax = push_bound(S);  // (leaf folding: no push to an id >= n_core)
   const auto t0 = std::chrono::steady_clock::now();
   bool bm_ok = false;  // the previous level of this batch wrote the frontier bitmap
   const int rg = std::max(1, std::min(64, grid / 32));
@@ -137,7 +139,7 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
   auto ef_stop_for = [&](uint32_t level) -> unsigned long long {
     if (opt.force_dir == 1) return ~0ull;
     double efs = (double)S.ea / alpha_eff();
-    if (tun_.gamma > 0 && level >= 2) efs = std::min(efs, gamma_for(level - 1) * (double)n_eff());
+    if (tun_.gamma > 0 && level >= 2) efs = std::min(efs, gamma_for(level - 1) * (double)extent(S));
     return (unsigned long long)std::max(0.0, std::min(efs, 1.8e19));
   };
   int aidx = 0;   // alive slot the next level reads
@@ -166,8 +168,14 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
           sm.gmask, done_.as<uint32_t>(), anyvis_.as<uint32_t>(), stamp_.as<int32_t>(), epoch_,
           fl_[S.fc ^ 1].as<int32_t>(), cur,
           slabF_.as<uint32_t>() + (size_t)(i - pend) * grid * 64 * W, prev,
-          bm_ok ? 1 : 0, i + 1 == K ? 1 : 0, i > 0 ? slots + i - 1 : nullptr, ef_stop_for(level));
+          bm_ok ? 1 : 0, i + 1 == K ? 1 : 0, i > 0 ? slots + i - 1 : nullptr, ef_stop_for(level),
+          vmax);
       MSBFS_HIP_CHECK(hipGetLastError());
+      if constexpr (!COUNT) {
+        if (S.fold)  // (a closed level appends nothing: its list is empty)
+          leaf_weigh<W>(R, aslot + 16 * aidx, level + 1, fl_[S.fc ^ 1].as<int32_t>(), 0,
+                        &cur->fl2.v, s);
+      }
       if (i + 1 - pend == red || i + 1 == K) reduce_pending(i + 1);
       S.fc ^= 1;
       S.ac ^= 1;
@@ -182,13 +190,15 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
           fl_[S.fc].as<int32_t>(), 0, &prev->fl2.v, g_.rowptr, g_.col, R,
           acc_[S.ac].as<uint64_t>(), done_.as<uint32_t>(), acc_[S.ac ^ 1].as<uint64_t>(),
           stamp_.as<int32_t>(), epoch_, touched_.as<int32_t>(), cur,
-          S.lazy ? anyvis_.as<uint32_t>() : nullptr, nullptr, i > 0 ? prev : nullptr, ef_stop_for(level));
+          S.lazy ? anyvis_.as<uint32_t>() : nullptr, nullptr, i > 0 ? prev : nullptr,
+          ef_stop_for(level), vmax);
     else
       k_td_expand_small<W, true><<<grid, kBlock, 0, s>>>(
           fl_[S.fc].as<int32_t>(), 0, &prev->fl2.v, g_.rowptr, g_.col, R, O,
           done_.as<uint32_t>(), acc_[S.ac ^ 1].as<uint64_t>(), stamp_.as<int32_t>(), epoch_,
           touched_.as<int32_t>(), cur, S.lazy ? anyvis_.as<uint32_t>() : nullptr,
-          S.osnap_next ? asnap_.as<uint32_t>() : nullptr, i > 0 ? prev : nullptr, ef_stop_for(level));
+          S.osnap_next ? asnap_.as<uint32_t>() : nullptr, i > 0 ? prev : nullptr,
+          ef_stop_for(level), vmax);
     k_td_finalize<W, FUSE><<<grid, kBlock, 0, s>>>(touched_.as<int32_t>(), g_.rowptr, R, O,
                                acc_[S.ac ^ 1].as<uint64_t>(), aslot + 16 * aidx, sm.gmask,
                                done_.as<uint32_t>(), fl_[S.fc ^ 1].as<int32_t>(), cur,
@@ -196,6 +206,11 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
                                S.fsrc_acc ? acc_[S.ac].as<uint64_t>() : nullptr,
                                anyvis_.as<uint32_t>(), slabF_.as<uint32_t>(), S.lazy ? 1 : 0,
                                &prev->act2.v);
+    if constexpr (!COUNT) {
+      if (S.fold)
+        leaf_weigh<W>(R, aslot + 16 * aidx, level + 1, fl_[S.fc ^ 1].as<int32_t>(), 0,
+                      &cur->fl2.v, s);
+    }
     if constexpr (!FUSE) {
       k_count_frontier<W, COUNT, false><<<grid, kBlock, 0, s>>>(
           fl_[S.fc ^ 1].as<int32_t>(), cur, g_.rowptr, acc_[S.ac ^ 1].as<uint64_t>(), nullptr,

@@ -205,6 +205,7 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
   MSBFS_HIP_CHECK(hipMemsetAsync(anyvis_.p, 0, anyvis_.bytes, s));
   MSBFS_HIP_CHECK(hipMemsetAsync(ctr_.p, 0, sizeof(Ctr), s));
   MSBFS_HIP_CHECK(hipMemsetAsync(small_.p, 0, small_.bytes, s));
+  if (!S.fold) leaf_.rows_dirty = true;  // (this batch writes leaf rows; see LeafState)
   const Small sm = small();
   // ---- sources: (vertex, local group) pairs, out-of-range ids dropped (main.cu:49)
   std::vector<int32_t> hp, hk;
@@ -248,6 +249,7 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
                                    hipMemcpyHostToDevice, s));
   }
   ++epoch_;
+  if (S.fold) leaf_.first.ensure((size_t)np1);  // (sized by prepare_queries before a timed run)
   if (np) {
     k_zero_src_rows<W><<<grid_for(np * W, kBlock), kBlock, 0, s>>>(
         dpv, np, g_.old2new, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>());
@@ -255,8 +257,12 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
     k_init<W, COUNT><<<grid_for(np, kBlock), kBlock, 0, s>>>(
         dpv, dpk, np, g_.rowptr, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>(),
         acc_[S.ac].as<uint64_t>(), stamp_.as<int32_t>(), epoch_, fl_[S.fc].as<int32_t>(),
-        ctr_.as<Ctr>(), sm.E, sm.alive[0], anyvis_.as<uint32_t>(), g_.old2new);
+        ctr_.as<Ctr>(), sm.E, sm.alive[0], anyvis_.as<uint32_t>(), g_.old2new,
+        S.fold ? leaf_.first.as<uint8_t>() : nullptr);
     MSBFS_HIP_CHECK(hipGetLastError());
+    if constexpr (!COUNT) {
+      if (S.fold) leaf_sources<W>(dpv, dpk, np, s);  // (+ level 0's weighted count)
+    }
     if constexpr (COUNT) record_sources(dpv, dpk, np, W, s);  // (a distance run's level 0)
   }
   const HostCtr c = read_ctr(s);  // also retires the pinned/host source copies
@@ -292,7 +298,7 @@ void BitparSolver::levels(Loop& S, RunStats* st, hipStream_t s) {
       // graphs never get there). Tuning gamma scales the vertex test (0 turns it off).
       bottom_up = (double)S.ef > (double)S.ea / alpha_eff() ||
                   (tun_.gamma > 0 && S.level >= 1 &&
-                   (double)S.ef > gamma_for(S.level) * (double)n_eff());
+                   (double)S.ef > gamma_for(S.level) * (double)extent(S));
     else bottom_up = keep_pulling((double)S.nf, (double)S.ef, (double)S.na, (double)S.ea, opt.beta,
                                   alpha_eff());
     const std::string& dirs = tun_.dirs;
@@ -337,6 +343,15 @@ void BitparSolver::levels(Loop& S, RunStats* st, hipStream_t s) {
       MSBFS_HIP_CHECK(hipGetLastError());
     }
     c = read_ctr(s);
+    if constexpr (!COUNT) {
+      if (S.fold) {
+        // the level's buffer and alive mask (neither index has flipped yet: the swaps are below);
+        // the new frontier's list where it is short against the parents, and a list at all
+        const bool by_list = !S.fl_bitmap && (int64_t)c.fl2 * 4 < leaf_.nsmall + leaf_.nheavy;
+        leaf_weigh<W>(vis_[S.cur].as<uint64_t>(), sm.alive[S.alv], S.level + 1,
+                      by_list ? fl_[S.fc ^ 1].as<int32_t>() : nullptr, (int64_t)c.fl2, nullptr, s);
+      }
+    }
     if (S.lean_ran) {
       // (high-diameter graphs: most vertices need more than their first neighbour; once a lean
       // pass sends over a quarter of its vertices on, the batch keeps the regular pull)
@@ -367,10 +382,10 @@ void BitparSolver::levels(Loop& S, RunStats* st, hipStream_t s) {
     if (trace) {
       fprintf(stderr,
               "[msbfs bp W=%d] level %u %s%c nf=%lld ef=%lld -> nf'=%lld ef'=%lld touched=%u "
-              "active=%lld (wide %lld) ea=%lld ev=%lld  %.3f ms\n",
+              "active=%lld (wide %lld) ea=%lld ev=%lld%s  %.3f ms\n",
               W, S.level, bottom_up ? "BU" : "TD", bottom_up ? S.kind : ' ', (long long)S.nf, (long long)S.ef,
               (long long)c.fl2, (long long)c.ef2, c.touched, (long long)S.na, (long long)S.nactw,
-              (long long)S.ea, (long long)(S.ev + (long long)c.ev2), lms);
+              (long long)S.ea, (long long)(S.ev + (long long)c.ev2), S.fold ? " L" : "", lms);
     }
     tl = t2;
     S.nf = c.fl2;
@@ -387,13 +402,23 @@ template <int W, bool COUNT>
 void BitparSolver::batch_impl(int64_t k0, int64_t nb, const int64_t* qoff, const int32_t* qids,
                               int64_t* Fout, int64_t* edges2, RunStats* st, hipStream_t s) {
   Loop S;
-  S.cnt = n_eff();
+  S.fold = leaf_fold_for(COUNT, 1, false, s);
+  S.cnt = extent(S);
+  if constexpr (!COUNT) {
+    if (S.fold) leaf_begin<W>(S, s);
+  }
   // lazy: no per-batch fill of vis_[0] (n_eff * 8W bytes, ~0.8 ms on RMAT-26); the edge-counting
   // pass re-reads both rows of every new vertex (k_count_frontier), so it keeps the fill
   S.lazy = tun_.lazy && !COUNT && !fused_batches<COUNT>();
   start_batch<W, COUNT>(k0, nb, qoff, qids, S, s);
   levels<W, COUNT>(S, st, s);
   // frontier is empty: accumulator entries were cleared by finalize / zero_acc
+  if constexpr (!COUNT) {
+    if (S.fold) {
+      leaf_end<W>(pairs_.as<int32_t>(), S.nsrc, s);
+      if (st) st->leaf_folded = n_eff() - leaf_.n_core;
+    }
+  }
   const unsigned long long* h = read_small(s);
   for (int64_t k = 0; k < nb; ++k) {
     Fout[k] = (int64_t)h[k];

@@ -14,7 +14,8 @@ namespace bp {
 
 namespace {
 void greedy_tiles(const std::vector<int32_t>& plen, int64_t cnt, int part, int nparts,
-                  std::vector<PfxTile>& tiles, std::vector<int32_t>& big, int64_t& nent) {
+                  std::vector<PfxTile>& tiles, std::vector<int32_t>& big, int64_t& nent,
+                  int64_t brk, int64_t& t_brk) {
   constexpr int VT = kTileVT, VWT = kVertexWeight;
   int64_t e = 0;
   int32_t v0 = 0;
@@ -25,9 +26,14 @@ void greedy_tiles(const std::vector<int32_t>& plen, int64_t cnt, int part, int n
     nv = 0;
     w = 0;
   };
+  t_brk = -1;
   for (int64_t i = 0; i < cnt; ++i) {
     const int32_t v = (int32_t)(part + i * nparts);
     const int64_t p = plen[(size_t)i];
+    if (i == brk) {  // (a tile ends here: a folded run launches only the tiles before it)
+      close();
+      t_brk = (int64_t)tiles.size();
+    }
     if (p > kBigPrefix) {
       close();
       big.push_back(v);
@@ -47,6 +53,7 @@ void greedy_tiles(const std::vector<int32_t>& plen, int64_t cnt, int part, int n
     e += p;
   }
   close();
+  if (t_brk < 0) t_brk = (int64_t)tiles.size();
   tiles.push_back(PfxTile{0, 0, e});  // sentinel: ends the last tile
   nent = e;
 }
@@ -101,7 +108,9 @@ const BitparSolver::TileSet* BitparSolver::pfx_tiles(int W, int part, int nparts
   std::vector<PfxTile> tl;
   std::vector<int32_t> big;
   int64_t nent = 0;
-  greedy_tiles(hp, cnt, part, nparts, tl, big, nent);
+  // (leaf folding, bitpar/leaf.hpp: one set of tiles per graph, broken at the first leaf)
+  int64_t t_core = 0;
+  greedy_tiles(hp, cnt, part, nparts, tl, big, nent, nparts == 1 ? leaf_n_core() : -1, t_core);
   const size_t pb = (size_t)std::max<int64_t>(nent, 1) * sizeof(uint32_t);
   const size_t tb = tl.size() * sizeof(PfxTile), bb = std::max<size_t>(big.size(), 1) * 4;
   size_t fr = 0, tot = 0;
@@ -125,6 +134,7 @@ const BitparSolver::TileSet* BitparSolver::pfx_tiles(int W, int part, int nparts
   T.ntiles = (int64_t)tl.size() - 1;
   T.nbig = (int64_t)big.size();
   T.nent = nent;
+  T.t_core = t_core;
   T.ti.resize((size_t)T.ntiles + 1);
   T.te.resize((size_t)T.ntiles + 1);
   for (int64_t t = 0; t < T.ntiles; ++t) {
@@ -239,7 +249,9 @@ int BitparSolver::tiles_pull(Loop& S, hipStream_t s, const uint64_t* R, uint64_t
   // range order. (Every rank hands its pieces out in this same order: the collectives pair up.)
   for (int k = 0; k < nch; ++k) {
     const int c = nch - 1 - k;
-    const int64_t t0 = tile_at(c), t1 = tile_at(c + 1);
+    // (a folded run has one range: its tiles end at the first leaf)
+    const int64_t t0 = tile_at(c);
+    const int64_t t1 = S.fold ? std::min(tile_at(c + 1), T->t_core) : tile_at(c + 1);
     if (t1 > t0) {
       if (rows + grid > 3 * kMaxGrid) fail("tiled pull: counter slab rows exhausted");
       auto kt = S.push_after ? k_pfx_tiles<W, false> : k_pfx_tiles<W, true>;

@@ -38,7 +38,8 @@ ChunkFn = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int64, C.c_int64)
 
 class Stats(C.Structure):
     _fields_ = [("levels", C.c_int64), ("td_levels", C.c_int64), ("bu_levels", C.c_int64),
-                ("batches", C.c_int64), ("device_ms", C.c_double), ("builds", C.c_int64)]
+                ("batches", C.c_int64), ("device_ms", C.c_double), ("builds", C.c_int64),
+                ("leaf_folded", C.c_int64)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -125,6 +126,10 @@ def _sig(lib):
         "msbfs_solver_free": (None, [vp]),
         "msbfs_solver_levels": (C.c_int64, [vp, P(Level), C.c_int64]),
         "msbfs_argmin": (C.c_int64, [i64p, C.c_int64]),
+        "msbfs_leaf_fold_on": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int64, C.c_int64]),
+        "msbfs_leaf_fold_lists": (C.c_int, [C.c_int64, i64p, i32p, i64p, i32p, C.c_int64, i32p,
+                                            i32p, i32p]),
         "msbfs_hybrid_extent": (C.c_int, [vp, i64p]),
         "msbfs_solver_hybrid_max_groups": (C.c_int64, [vp]),
         "msbfs_solver_hybrid_phase_a": (C.c_int, [vp, C.c_int64, i64p, i32p, C.c_int, C.c_int,
