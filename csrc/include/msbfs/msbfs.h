@@ -105,6 +105,8 @@ int msbfs_cpu_run_parents(int64_t n, const int64_t* rowptr, const int32_t* col, 
 /* ---- device graphs ---- */
 int msbfs_graph_from_host_csr(int device, int64_t n, const int64_t* rowptr, const int32_t* col,
                               msbfs_graph* out);
+/* m edges (d_u[i], d_v[i]) in device memory; an id outside [0, n) fails with the lowest such
+ * edge's index, nothing is written out of range */
 int msbfs_graph_from_device_edges(int device, int64_t n, int64_t m, const int32_t* d_u,
                                   const int32_t* d_v, msbfs_graph* out);
 int msbfs_graph_wrap_device(int device, int64_t n, int64_t nnz, int64_t* d_rowptr, int32_t* d_col,

@@ -58,12 +58,19 @@ __global__ __launch_bounds__(kBlock) void k_uniform_pass(uint64_t seed, int64_t 
   }
 }
 
+// Edges from two device arrays: count (scatter = 0) or scatter both directions. An id outside
+// [0, n) records the lowest offending edge index in *bad and is skipped, as in k_pairs_pass.
 __global__ __launch_bounds__(kBlock) void k_edges_pass(const int32_t* eu, const int32_t* ev,
-                                                       int64_t m, unsigned long long* cnt,
-                                                       int32_t* col, int scatter) {
+                                                       int64_t m, int64_t n,
+                                                       unsigned long long* cnt, int32_t* col,
+                                                       int scatter, unsigned long long* bad) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
     const int32_t u = eu[i], v = ev[i];
+    if ((uint32_t)u >= (uint64_t)n || (uint32_t)v >= (uint64_t)n) {
+      atomicMin(bad, (unsigned long long)i);
+      continue;
+    }
     if (!scatter) {
       atomicAdd(&cnt[u], 1ull);
       atomicAdd(&cnt[v], 1ull);
@@ -256,19 +263,28 @@ void device_graph_from_host(DeviceGraph& g, int64_t n, const int64_t* rowptr, co
 
 void device_graph_from_edges(DeviceGraph& g, int64_t n, int64_t m, const int32_t* d_u,
                              const int32_t* d_v, hipStream_t s) {
+  if (m < 0) fail("edge count must not be negative");
   alloc_rowptr(g, n);
   g.m = m;
   DevBuf cnt((size_t)std::max<int64_t>(n, 1) * sizeof(int64_t));
   MSBFS_HIP_CHECK(hipMemsetAsync(cnt.p, 0, cnt.bytes, s));
+  DevBuf bad(sizeof(unsigned long long));
+  MSBFS_HIP_CHECK(hipMemsetAsync(bad.p, 0xFF, bad.bytes, s));
   if (m) {
-    k_edges_pass<<<grid_for(m, kBlock), kBlock, 0, s>>>(d_u, d_v, m, cnt.as<unsigned long long>(),
-                                                       nullptr, 0);
+    k_edges_pass<<<grid_for(m, kBlock), kBlock, 0, s>>>(d_u, d_v, m, n,
+                                                       cnt.as<unsigned long long>(), nullptr, 0,
+                                                       bad.as<unsigned long long>());
     MSBFS_HIP_CHECK(hipGetLastError());
+    unsigned long long b = ~0ull;
+    MSBFS_HIP_CHECK(hipMemcpyAsync(&b, bad.p, sizeof(b), hipMemcpyDeviceToHost, s));
+    MSBFS_HIP_CHECK(hipStreamSynchronize(s));
+    if (b != ~0ull) fail("edge " + std::to_string(b) + " has a vertex id outside [0, n)");
   }
   build_from_counts(g, cnt, s);
   if (m) {
-    k_edges_pass<<<grid_for(m, kBlock), kBlock, 0, s>>>(d_u, d_v, m, cnt.as<unsigned long long>(),
-                                                       g.col, 1);
+    k_edges_pass<<<grid_for(m, kBlock), kBlock, 0, s>>>(d_u, d_v, m, n,
+                                                       cnt.as<unsigned long long>(), g.col, 1,
+                                                       bad.as<unsigned long long>());
     MSBFS_HIP_CHECK(hipGetLastError());
   }
   device_graph_stats(g, s);
@@ -281,7 +297,11 @@ void device_graph_from_edges(DeviceGraph& g, int64_t n, int64_t m, const int32_t
 template <class F>
 static void stream_edges(const EdgeFileMap& f, int2* dst, hipStream_t s, F&& fn) {
   constexpr int64_t kPiece = int64_t(1) << 25;  // edges per piece (256 MB)
-  const int64_t piece = std::min<int64_t>(kPiece, std::max<int64_t>(f.m, 1));
+  // MSBFS_EDGE_PIECE=<edges> makes the pieces smaller (tests: a small file in many pieces)
+  int64_t want = kPiece;
+  if (const char* e = getenv("MSBFS_EDGE_PIECE"))
+    if (*e) want = std::min<int64_t>(kPiece, std::max<int64_t>(atoll(e), 1));
+  const int64_t piece = std::min<int64_t>(want, std::max<int64_t>(f.m, 1));
   PinnedBuf pin0((size_t)piece * 8), pin1((size_t)piece * 8);
   PinnedBuf* pin[2] = {&pin0, &pin1};
   DevBuf dpiece[2];
@@ -315,11 +335,14 @@ void device_graph_from_edge_file(DeviceGraph& g, const std::string& path, hipStr
   DevBuf bad(sizeof(unsigned long long));
   MSBFS_HIP_CHECK(hipMemsetAsync(bad.p, 0xFF, bad.bytes, s));
   // the whole edge list in HBM when it fits next to the CSR (one pass over the file: count and
-  // scatter read the device copy); otherwise the file is streamed twice
+  // scatter read the device copy); otherwise the file is streamed twice.
+  // MSBFS_EDGE_RESIDENT=0|1 forces one mode (tests)
   size_t fr = 0, tot = 0;
   MSBFS_HIP_CHECK(hipMemGetInfo(&fr, &tot));
   const size_t ebytes = (size_t)m * 8, cbytes = (size_t)m * 8 + (size_t)n * 24;
-  const bool resident = ebytes + cbytes + (size_t(4) << 30) < fr;
+  bool resident = ebytes + cbytes + (size_t(4) << 30) < fr;
+  if (const char* e = getenv("MSBFS_EDGE_RESIDENT"))
+    if (*e) resident = atoi(e) != 0;
   DevBuf all;
   if (resident && m) all.alloc(ebytes);
   auto pass = [&](int scatter) {

@@ -181,6 +181,29 @@ class DeviceGraph:
         return g.relabel_by_degree() if relabel else g
 
     @classmethod
+    def from_device_edges(cls, n: int, u_t, v_t, device: int = 0,
+                          relabel: bool = False) -> "DeviceGraph":
+        """Build the CSR from an edge list that is already in HBM: two int32 torch tensors of
+        equal length on `device` (read, not kept). An id outside [0, n) raises MsbfsError with
+        the lowest such edge's index."""
+        import torch
+        for t in (u_t, v_t):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise TypeError("from_device_edges takes int32 torch tensors")
+            if t.device.type != "cuda" or t.device.index != device:
+                raise ValueError(f"from_device_edges: the tensors must live on cuda:{device}")
+        if u_t.dim() != 1 or v_t.dim() != 1 or u_t.numel() != v_t.numel():
+            raise ValueError("from_device_edges: u and v must be 1-D and equally long")
+        u_t, v_t = u_t.contiguous(), v_t.contiguous()
+        torch.cuda.current_stream(device).synchronize()  # (the build runs on the null stream)
+        h = C.c_void_p()
+        native.check(native.lib().msbfs_graph_from_device_edges(
+            device, n, int(u_t.numel()), C.c_void_p(u_t.data_ptr()), C.c_void_p(v_t.data_ptr()),
+            C.byref(h)))
+        g = cls(h, device)
+        return g.relabel_by_degree() if relabel else g
+
+    @classmethod
     def uniform(cls, n: int, m: int, seed: int = 1, device: int = 0) -> "DeviceGraph":
         h = C.c_void_p()
         native.check(native.lib().msbfs_graph_gen_uniform(device, n, m, seed, C.byref(h)))

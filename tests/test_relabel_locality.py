@@ -7,25 +7,11 @@ two relabels of one graph agree."""
 import numpy as np
 import pytest
 
+from degree_graphs import _oracle_map
+
 pytestmark = pytest.mark.gpu
 
 VAR = "MSBFS_RELABEL_LOCALITY"
-
-
-def _oracle_map(host):
-    """old2new for (degree descending, key2 ascending, old id ascending), key2[v] = the smallest
-    id, in the degree-only order, among v's neighbours (UINT32_MAX for an isolated vertex)."""
-    n = host.n
-    ids = np.arange(n, dtype=np.int64)
-    deg = np.diff(host.rowptr)
-    prov = np.empty(n, np.int64)
-    prov[np.lexsort((ids, -deg))] = ids
-    key2 = np.full(n, np.iinfo(np.uint32).max, np.int64)
-    rows = np.flatnonzero(deg > 0)
-    key2[rows] = np.minimum.reduceat(prov[host.col], host.rowptr[rows])
-    o2n = np.empty(n, np.int64)
-    o2n[np.lexsort((ids, key2, -deg))] = ids
-    return o2n, deg
 
 
 def _relabelled(make, monkeypatch, locality, regen=None):
