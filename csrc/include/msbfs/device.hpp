@@ -305,6 +305,12 @@ inline int grid_for(int64_t items, int per_block, int cap = 2048) {
   if (g > cap) g = cap;
   return (int)g;
 }
+// `grid` blocks of a grid-stride kernel, at most max_grid of them where max_grid > 0 (the
+// bit-parallel solver's test key max_grid: a block then runs as many tiles of a small graph as
+// only a huge one gives it otherwise); 0: as computed
+inline int grid_capped(int grid, int max_grid) {
+  return max_grid > 0 && grid > max_grid ? max_grid : grid;
+}
 
 }  // namespace msbfs
 

@@ -59,13 +59,19 @@ void Tuning::set(const std::string& key, const std::string& v) {
     leaf = (int)to_num(key, v);
     if (leaf < -1 || leaf > 1) fail("tuning: leaf must be 0 (off), 1 (on where legal) or -1 (auto)");
   }
+  else if (key == "max_grid") {
+    const double x = to_num(key, v);  // (range test before the narrowing)
+    if (!(x >= 0 && x <= 2048) || x != (double)(int)x)
+      fail("tuning: max_grid must be 0 (no cap) or a block count in [1, 2048]");
+    max_grid = (int)x;
+  }
   else if (key == "dirs") {
     for (char c : v)
       if (c != 'T' && c != 'B' && c != '.') fail("tuning: dirs takes T, B or . per level");
     dirs = v;
   } else {
     fail("tuning: unknown key '" + key +
-         "' (gamma gamma2 pfx codes code_deg lean lean_min lazy td_fused td_bm batch bu_max tiles tiles_code_deg full dskip push_after dskip3 chunk2 wide_few pfx_h filter_frac tiles_w leaf dirs)");
+         "' (gamma gamma2 pfx codes code_deg lean lean_min lazy td_fused td_bm batch bu_max tiles tiles_code_deg full dskip push_after dskip3 chunk2 wide_few pfx_h filter_frac tiles_w leaf max_grid dirs)");
   }
 }
 

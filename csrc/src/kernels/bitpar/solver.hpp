@@ -482,6 +482,8 @@ class BitparSolver final : public Solver {
     if (Lay<W>::VPW == 64) return std::min(g, 5 * cus);
     return batch ? std::min(g, 4 * cus) : g;
   }
+  // the block count of a grid-stride level kernel under the test key max_grid (0: unchanged)
+  int cap(int grid) const { return grid_capped(grid, tun_.max_grid); }
   int num_cus() {  // (compute units of the solver's GPU, queried once)
     if (num_cus_ == 0) {
       hipDeviceProp_t prop;

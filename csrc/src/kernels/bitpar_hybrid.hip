@@ -100,7 +100,7 @@ void BitparSolver::code_send(const uint64_t* vis, uint64_t* staging, int64_t cnt
   for (int j = 0; j < nparts; ++j) coded_len[j] = 0;
   if (c == 0) return;
   const CodeWs w = code_ws(c);
-  k_pack_words<W><<<grid_for(cnt, Lay<W>::TILE, 8192), kBlock, 0, s>>>(
+  k_pack_words<W><<<cap(grid_for(cnt, Lay<W>::TILE, 8192)), kBlock, 0, s>>>(
       vis, g_.rowptr, part, nparts, cnt, ws.b[nparts], ws, staging, 0, cnt);
   MSBFS_HIP_CHECK(hipGetLastError());
   const int gc = grid_for((c + kCodeCPW - 1) / kCodeCPW * 64, kBlock, 1 << 20);
@@ -168,7 +168,7 @@ void BitparSolver::phase_a_impl(int64_t K, const int64_t* qoff, const int32_t* q
   // pack own-vertex range [i0, i1) of buffer vis into its place in send
   auto pack = [&](const uint64_t* vis, int64_t i0, int64_t i1) {
     if (i1 <= i0) return;
-    k_pack_words<W><<<grid_for(i1 - i0, Lay<W>::TILE, 8192), kBlock, 0, s>>>(
+    k_pack_words<W><<<cap(grid_for(i1 - i0, Lay<W>::TILE, 8192)), kBlock, 0, s>>>(
         vis, g_.rowptr, part, nparts, S.cnt, wt, ws, send, i0, i1);
     MSBFS_HIP_CHECK(hipGetLastError());
   };
@@ -184,7 +184,7 @@ void BitparSolver::phase_a_impl(int64_t K, const int64_t* qoff, const int32_t* q
   start_batch<W, false>(0, K, qoff, qids, S, s);
   levels<W, false>(S, st, s);
   if (S.fsrc_acc && S.nf > 0) {  // stopped after a top-down level: restore the zero accumulator
-    k_zero_acc<W><<<grid_for(S.nf * Lay<W>::G, kBlock), kBlock, 0, s>>>(
+    k_zero_acc<W><<<cap(grid_for(S.nf * Lay<W>::G, kBlock)), kBlock, 0, s>>>(
         fl_[S.fc].as<int32_t>(), S.nf, acc_[S.ac].as<uint64_t>());
     MSBFS_HIP_CHECK(hipGetLastError());
   }
@@ -247,7 +247,7 @@ void BitparSolver::phase_c_impl(int64_t K, int w_begin, int w_count, int nparts,
   if (n_eff > 0) {  // vertices >= n_eff have no edges: no kernel reads their rows or bits
     PartPrefix pre{};
     for (int r = 0; r < nparts; ++r) pre.b[r + 1] = pre.b[r] + part_count(n_eff, r, nparts);
-    k_hybrid_setup<W><<<grid_for(n_eff, Lay<W>::TILE, 8192), kBlock, 0, s>>>(
+    k_hybrid_setup<W><<<cap(grid_for(n_eff, Lay<W>::TILE, 8192)), kBlock, 0, s>>>(
         recv, w_count, n_eff, nparts, pre, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>(),
         sm.alive[0], sm.gmask, done_.as<uint32_t>(), anyvis_.as<uint32_t>(), g_.rowptr,
         std::max(opt.wide_degree, kWideLater), act_[0].as<int32_t>(), actw_[0].as<int32_t>(),

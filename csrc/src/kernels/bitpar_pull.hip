@@ -193,7 +193,7 @@ void BitparSolver::fix_done_rows(Loop& S, hipStream_t s) {
   S.skip_pending = false;
   if (S.nf <= 0) return;
   const Small sm = small();
-  k_fix_done_rows<W><<<grid_for(S.nf, Lay<W>::TILE, kMaxGrid), kBlock, 0, s>>>(
+  k_fix_done_rows<W><<<cap(grid_for(S.nf, Lay<W>::TILE, kMaxGrid)), kBlock, 0, s>>>(
       fl_[S.fc].as<int32_t>(), nullptr, S.nf, done_.as<uint32_t>(),
       vis_[S.cur ^ 1].as<uint64_t>(), vis_[S.cur].as<uint64_t>(), S.skip_alive, sm.gmask);
   MSBFS_HIP_CHECK(hipGetLastError());
@@ -307,7 +307,7 @@ void BitparSolver::bu_tail_push(Loop& S, BuLevel& L, hipStream_t s) {
   if (!p.tail_push) return;
   ++epoch_;
   const int split = S.nf < 65536 ? 8 : 1;  // (see k_push_tail)
-  k_push_tail<W><<<grid_for(S.nf * 64 * split, kBlock, 8192), kBlock, 0, s>>>(
+  k_push_tail<W><<<cap(grid_for(S.nf * 64 * split, kBlock, 8192)), kBlock, 0, s>>>(
       fl_[S.fc].as<int32_t>(), S.nf, L.H, g_.rowptr, g_.col, L.R, L.codes, L.code_from,
       p.tiled ? nullptr : done_.as<uint32_t>(), S.part, S.nparts, acc_[S.ac].as<uint64_t>(),
       (p.tiled || p.pfx_nostamp) ? nullptr : stamp_.as<int32_t>(), epoch_, split, push_bound(S));
@@ -324,7 +324,7 @@ void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
   if (p.kind == PullKind::Tiled) {
     L.rows = tiles_pull<W>(S, s, L.R, L.O, L.snap, L.codes, L.code_from, L.rows);
     if (S.push_after) {
-      const int gp = grid_for(S.nf * 64, kBlock, kMaxGrid);
+      const int gp = cap(grid_for(S.nf * 64, kBlock, kMaxGrid));
       if (L.rows + gp > 3 * kMaxGrid) fail("tail push: counter slab rows exhausted");
       k_push_tail_after<W><<<gp, kBlock, 0, s>>>(
           fl_[S.fc].as<int32_t>(), S.nf, kPfxH, g_.rowptr, g_.col, L.R, L.codes, L.code_from, L.O,
@@ -343,11 +343,11 @@ void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
              slabF<W>(L.rows)};
   a.filter_from = p.filter_from;
   a.snap = L.snap;
-  const int gn = grid_for(S.nact, Lw::TILE, kMaxGrid);  // (the 256-thread kernels)
+  const int gn = cap(grid_for(S.nact, Lw::TILE, kMaxGrid));  // (the 256-thread kernels)
   switch (p.kind) {
     case PullKind::Prefix: {
       using Cfg = NarrowPrefix<W, FUSE>;
-      const int g = grid_for(S.nact, (Cfg::BT / 64) * Lw::VPW, 512);
+      const int g = cap(grid_for(S.nact, (Cfg::BT / 64) * Lw::VPW, 512));
       if (Cfg::FBM) a.fl2 = reinterpret_cast<int32_t*>(fbm_tile_.p);
       a.pacc = acc_[S.ac].as<uint64_t>();
       a.stamp = p.pfx_nostamp ? nullptr : stamp_.as<int32_t>();
@@ -358,7 +358,7 @@ void BitparSolver::bu_narrow(Loop& S, BuLevel& L, hipStream_t s) {
       break;
     }
     case PullKind::Hub: {
-      const int g = grid_for(S.nact, (NarrowHub<FUSE>::BT / 64) * Lw::VPW, 512);
+      const int g = cap(grid_for(S.nact, (NarrowHub<FUSE>::BT / 64) * Lw::VPW, 512));
       if (p.hub_big) launch_narrow<W, NarrowHubBig<FUSE>>(g, a, s, &p);
       else launch_narrow<W, NarrowHub<FUSE>>(g, a, s, &p);
       if (FUSE) L.rows += g;
@@ -447,7 +447,7 @@ void BitparSolver::bu_wide(Loop& S, BuLevel& L, hipStream_t s) {
                                                                 chunk_cnt_.as<int64_t>());
     MSBFS_HIP_CHECK(hipGetLastError());
     bu_chunks<W>(S, L, d, chunk_cnt_.as<int64_t>(), S.nactw, s);
-    k_chunk_rest_count<W><<<grid_for(S.nactw, Lw::TILE, kMaxGrid), kBlock, 0, s>>>(
+    k_chunk_rest_count<W><<<cap(grid_for(S.nactw, Lw::TILE, kMaxGrid)), kBlock, 0, s>>>(
         lw, S.nactw, g_.rowptr, L.R, acc_[S.ac].as<uint64_t>(), L.alive, L.sm.gmask, L.snap, cnt);
     MSBFS_HIP_CHECK(hipGetLastError());
     inclusive_scan_i64(cnt, offs_.as<int64_t>(), S.nactw, t2, tb, s);
@@ -469,7 +469,7 @@ void BitparSolver::bu_wide(Loop& S, BuLevel& L, hipStream_t s) {
     MSBFS_HIP_CHECK(hipGetLastError());
     bu_chunks<W>(S, L, d, offs_.as<int64_t>() + S.nactw - 1, chunks_max, s);
   }
-  const int gw = grid_for(S.nactw, Lw::TILE, kMaxGrid);
+  const int gw = cap(grid_for(S.nactw, Lw::TILE, kMaxGrid));
   auto kw = p.fbm_out ? k_bu_wide_finalize<W, FUSE, true> : k_bu_wide_finalize<W, FUSE>;
   kw<<<gw, kBlock, 0, s>>>(
       lw, S.nactw, g_.rowptr, L.R, L.O, acc_[S.ac].as<uint64_t>(), L.alive, L.sm.gmask,
@@ -514,7 +514,7 @@ int BitparSolver::level_bu(Loop& S, hipStream_t s) {
   if (S.fsrc_acc) {
     // bottom-up does not read frontier bits; clear the pending top-down ones so acc_[ac]
     // is all-zero and can collect the wide vertices' chunk results
-    k_zero_acc<W><<<grid_for(S.nf * Lay<W>::G, kBlock), kBlock, 0, s>>>(
+    k_zero_acc<W><<<cap(grid_for(S.nf * Lay<W>::G, kBlock)), kBlock, 0, s>>>(
         fl_[S.fc].as<int32_t>(), S.nf, acc_[S.ac].as<uint64_t>());
     MSBFS_HIP_CHECK(hipGetLastError());
   }
@@ -526,14 +526,14 @@ int BitparSolver::level_bu(Loop& S, hipStream_t s) {
   if constexpr (COUNT) {
     // the edge-counting mode's count pass (the traversal kernels fuse the plain counts):
     // new frontier bits = Wb & ~R (both still in place: the swap is below)
-    const int gc = grid_for(S.nact + S.nactw, Lay<W>::TILE, kMaxGrid);
+    const int gc = cap(grid_for(S.nact + S.nactw, Lay<W>::TILE, kMaxGrid));
     k_count_frontier<W, COUNT, true><<<gc, kBlock, 0, s>>>(
         fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(), g_.rowptr, L.O, L.R, slabF<W>(L.rows),
         slabE<W>(L.rows));
     MSBFS_HIP_CHECK(hipGetLastError());
     L.rows += gc;
     record_level<W, true>(fl_[S.fc ^ 1].as<int32_t>(), ctr_.as<Ctr>(), L.O, L.R,
-                          S.nact + S.nactw, kMaxGrid, S.level, s);
+                          S.nact + S.nactw, cap(kMaxGrid), S.level, s);
   }
   std::swap(act_[0], act_[1]);
   std::swap(actw_[0], actw_[1]);
@@ -567,9 +567,9 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
                              (uint32_t)S.nactw, (unsigned long long)S.ea, sm.alive[S.alv], aslot);
   MSBFS_HIP_CHECK(hipGetLastError());
   // lists only shrink: a vertex stays active at most, and keeps its side of the kWideLater split
-  const int gn = full_pull() ? full_grid<W>(grid_for(S.nact + S.nactw, L::TILE, kMaxGrid), S.nact, true)
-                             : grid_for(S.nact + S.nactw, L::TILE, kMaxGrid);
-  const int gw = S.nactw ? grid_for(S.nactw, L::TILE, kMaxGrid) : 0;
+  const int g0 = cap(grid_for(S.nact + S.nactw, L::TILE, kMaxGrid));
+  const int gn = full_pull() ? full_grid<W>(g0, S.nact, true) : g0;
+  const int gw = S.nactw ? cap(grid_for(S.nactw, L::TILE, kMaxGrid)) : 0;
   const int rows = gn + gw, rg = std::max(1, std::min(64, rows / 32));
   const double alpha = alpha_eff();
   const uint32_t level0 = S.level;
@@ -770,7 +770,7 @@ void BitparSolver::leaf_begin(Loop& S, hipStream_t s) {
 template <int W>
 void BitparSolver::leaf_end(const int32_t* pv, int64_t np, hipStream_t s) {
   if (np > 0) {
-    k_zero_src_rows<W><<<grid_for(np * W, kBlock), kBlock, 0, s>>>(
+    k_zero_src_rows<W><<<cap(grid_for(np * W, kBlock)), kBlock, 0, s>>>(
         pv, np, g_.old2new, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>());
     MSBFS_HIP_CHECK(hipGetLastError());
   }
@@ -780,7 +780,7 @@ void BitparSolver::leaf_end(const int32_t* pv, int64_t np, hipStream_t s) {
 template <int W>
 void BitparSolver::leaf_sources(const int32_t* pv, const int32_t* pk, int64_t np, hipStream_t s) {
   const Small sm = small();
-  k_leaf_sources<W><<<grid_for(np, kBlock), kBlock, 0, s>>>(
+  k_leaf_sources<W><<<cap(grid_for(np, kBlock)), kBlock, 0, s>>>(
       pv, pk, leaf_.first.as<uint8_t>(), np, g_.old2new, g_.rowptr, g_.col,
       vis_[0].as<uint64_t>(), anyvis_.as<uint32_t>(), (int32_t)leaf_.n_core, (int32_t)n_eff(),
       sm.F);
@@ -801,15 +801,15 @@ void BitparSolver::leaf_weigh(const uint64_t* R, const uint64_t* alive, uint32_t
                    anyvis_.as<uint32_t>(), done_.as<uint32_t>(), alive, sm.gmask, sm.F, weight};
   if (list) {
     // (a device-side length: these are the short lists of the late levels and the batches)
-    const int g = n_dev ? 64 : grid_for(n, kLeafU * L::TILE, 1024);
+    const int g = cap(n_dev ? 64 : grid_for(n, kLeafU * L::TILE, 1024));
     if (!n_dev && n <= 0) return;
     k_leaf_weigh_list<W><<<g, kBlock, 0, s>>>(a, list, n, n_dev, 0, (int32_t)leaf_.n_core);
   } else {
     if (leaf_.nsmall > 0)
-      k_leaf_weigh<W><<<grid_for(leaf_.nsmall, kLeafU * L::TILE, 8 * std::max(1, num_cus())),
+      k_leaf_weigh<W><<<cap(grid_for(leaf_.nsmall, kLeafU * L::TILE, 8 * std::max(1, num_cus()))),
                         kBlock, 0, s>>>(a, leaf_.nsmall);
     if (leaf_.nheavy > 0)
-      k_leaf_weigh_list<W><<<grid_for(leaf_.nheavy, kLeafU * L::TILE, 1024), kBlock, 0, s>>>(
+      k_leaf_weigh_list<W><<<cap(grid_for(leaf_.nheavy, kLeafU * L::TILE, 1024)), kBlock, 0, s>>>(
           a, nullptr, leaf_.nheavy, nullptr, leaf_.nsmall, (int32_t)leaf_.n_core);
   }
   MSBFS_HIP_CHECK(hipGetLastError());

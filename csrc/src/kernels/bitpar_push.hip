@@ -14,7 +14,7 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
   using L = Lay<W>;
   const int64_t n = g_.n;
   const Small sm = small();
-  const int grid = kMaxGrid;
+  const int grid = cap(kMaxGrid);
   int rows = 0;  // slab rows written by this level's counting kernels
   uint64_t* R = vis_[S.cur].as<uint64_t>();
   uint64_t* O = vis_[S.cur ^ 1].as<uint64_t>();
@@ -24,7 +24,7 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
   const int32_t vmax = push_bound(S);  // (leaf folding: no push to an id >= n_core)
   if (g_.max_degree <= kSmallDeg) {
     // low-degree graph: vertex-parallel expansion, no degree scan
-    const int eg = grid_for(S.nf, L::TILE, 4096);
+    const int eg = cap(grid_for(S.nf, L::TILE, 4096));
     if (S.fsrc_acc)
       k_td_expand_small<W, false><<<eg, kBlock, 0, s>>>(
           fl_[S.fc].as<int32_t>(), S.nf, nullptr, g_.rowptr, g_.col, R,
@@ -41,7 +41,7 @@ int BitparSolver::level_td(Loop& S, hipStream_t s) {
   } else {
   frontier_degree_scan(g_.rowptr, fl_[S.fc].as<int32_t>(), S.nf, offs_.as<int64_t>(),
                        scan_tmp_.p, scan_bytes_, s);
-  const int eg = grid_for(S.ef, L::TILE, 8192);
+  const int eg = cap(grid_for(S.ef, L::TILE, 8192));
   if (S.fsrc_acc)
     k_td_expand<W, false><<<eg, kBlock, 0, s>>>(
         fl_[S.fc].as<int32_t>(), S.nf, offs_.as<int64_t>(), g_.rowptr, g_.col, R,
@@ -123,7 +123,8 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
   const int tdg = W == 1 && fused_batches<COUNT>() && S.nf >= kTdWideFrontier
                       ? 5 * std::max(1, num_cus())
                       : (W >= 2 && fused_batches<COUNT>() ? 3 * std::max(1, num_cus()) : kTdGrid);
-  const int grid = (int)std::min<int64_t>(tdg, std::max<int64_t>(1, (n + L::TILE - 1) / L::TILE));
+  const int grid =
+      cap((int)std::min<int64_t>(tdg, std::max<int64_t>(1, (n + L::TILE - 1) / L::TILE)));
   uint64_t* R = vis_[S.cur].as<uint64_t>();
   uint64_t* O = vis_[S.cur ^ 1].as<uint64_t>();
   const uint32_t level0 = S.level;

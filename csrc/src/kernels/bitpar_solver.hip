@@ -99,7 +99,7 @@ static __global__ __launch_bounds__(kBlock) void k_record_sources(
 void BitparSolver::record_sources(const int32_t* pv, const int32_t* pk, int64_t np, int w,
                                   hipStream_t s) {
   if (!rec_.out || np <= 0) return;
-  k_record_sources<<<grid_for(np, kBlock), kBlock, 0, s>>>(
+  k_record_sources<<<cap(grid_for(np, kBlock)), kBlock, 0, s>>>(
       pv, pk, np, g_.n, rec_.nb, rec_.out + rec_.k0 * rec_.ld, rec_.ld,
       rec_.parent ? rec_.parent + rec_.k0 * rec_.ld : nullptr, rec_.seen, g_.old2new, w);
   MSBFS_HIP_CHECK(hipGetLastError());
@@ -199,7 +199,7 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
   const size_t vb = (size_t)std::max<int64_t>(n_eff(), 1) * W * sizeof(uint64_t);
   if (!S.lazy) MSBFS_HIP_CHECK(hipMemsetAsync(vis_[0].p, 0, vb, s));
   else if (S.cnt > 0 && S.nparts > 1)  // hybrid phase A: only the rows levels 1-2 read (see k_zero_part_rows)
-    k_zero_part_rows<W><<<grid_for(S.cnt * Lay<W>::G, kBlock, 8192), kBlock, 0, s>>>(
+    k_zero_part_rows<W><<<cap(grid_for(S.cnt * Lay<W>::G, kBlock, 8192)), kBlock, 0, s>>>(
         S.cnt, S.part, S.nparts, vis_[0].as<uint64_t>());
   MSBFS_HIP_CHECK(hipMemsetAsync(done_.p, 0, done_.bytes, s));
   MSBFS_HIP_CHECK(hipMemsetAsync(anyvis_.p, 0, anyvis_.bytes, s));
@@ -251,10 +251,10 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
   ++epoch_;
   if (S.fold) leaf_.first.ensure((size_t)np1);  // (sized by prepare_queries before a timed run)
   if (np) {
-    k_zero_src_rows<W><<<grid_for(np * W, kBlock), kBlock, 0, s>>>(
+    k_zero_src_rows<W><<<cap(grid_for(np * W, kBlock)), kBlock, 0, s>>>(
         dpv, np, g_.old2new, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>());
     MSBFS_HIP_CHECK(hipGetLastError());
-    k_init<W, COUNT><<<grid_for(np, kBlock), kBlock, 0, s>>>(
+    k_init<W, COUNT><<<cap(grid_for(np, kBlock)), kBlock, 0, s>>>(
         dpv, dpk, np, g_.rowptr, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>(),
         acc_[S.ac].as<uint64_t>(), stamp_.as<int32_t>(), epoch_, fl_[S.fc].as<int32_t>(),
         ctr_.as<Ctr>(), sm.E, sm.alive[0], anyvis_.as<uint32_t>(), g_.old2new,

@@ -222,7 +222,7 @@ int BitparSolver::tiles_pull(Loop& S, hipStream_t s, const uint64_t* R, uint64_t
   const int nch = S.on_chunk && S.chunk_b.size() >= 2 ? (int)S.chunk_b.size() - 1 : 1;
   auto finalize_big = [&] {
     if (!T->nbig) return;
-    const int gw = grid_for(T->nbig, Lay<W>::TILE, kMaxGrid);
+    const int gw = cap(grid_for(T->nbig, Lay<W>::TILE, kMaxGrid));
     k_bu_wide_finalize<W, true><<<gw, kBlock, 0, s>>>(
         T->big.as<int32_t>(), T->nbig, g_.rowptr, R, O, acc_[S.ac].as<uint64_t>(), alive,
         sm.gmask, done_.as<uint32_t>(), nullptr, nullptr, ctr_.as<Ctr>(),

@@ -372,6 +372,18 @@ static void tuning() {
   CHECK(fails_with("lean=", "bad value"));
   CHECK(fails_with("lean", "expected key=value"));
   CHECK(fails_with("pfx=1", "pfx must be"));
+  // the test key max_grid: 0 (default, no cap) or a block count of 1..2048
+  CHECK(Tuning().max_grid == 0 && t.max_grid == 0);
+  for (const int g : {0, 1, 3, 2048}) {
+    Tuning m;
+    m.parse("max_grid=" + std::to_string(g));
+    CHECK(m.max_grid == g);
+  }
+  CHECK(fails_with("max_grid=-1", "max_grid must be"));
+  CHECK(fails_with("max_grid=4096", "max_grid must be"));
+  CHECK(fails_with("max_grid=2049", "max_grid must be"));
+  CHECK(fails_with("max_grid=1.5", "max_grid must be"));
+  CHECK(fails_with("nosuch=1", "max_grid"));  // (the unknown-key message lists it)
 }
 }  // namespace plan_test
 

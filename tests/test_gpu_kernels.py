@@ -353,6 +353,20 @@ def test_bitpar_tiled_first_pull(msbfs_pkg, K):
         words = 16 if K > 512 else 8 if K > 256 else 4
         tiled = tun.get("tiles", 1) and words >= tun.get("tiles_w", 8)
         assert tr[1]["level"] == 2 and tr[1]["kind"] == ("t" if tiled else "p"), (name, tr[1])
+        if name == "tiles" and tiled:
+            # Reach: k_pfx_tiles' GroupCounts<W, 5, ...> spill after 2^5 - 1 epilogue passes of a
+            # wave, so this level runs that path if some wave gets 32. Every vertex still active
+            # after the level went through a pass (128 / words vertices each) unless it is one of
+            # the big vertices (more than 1024 prefix entries: fewer than nnz / 1024); the grid
+            # is one block of 16 waves per CU.
+            # Open gap: at 4 words (the tiles4 runs, tiles_w = 4) a pass takes 32 vertices but a
+            # tile holds fewer, and this bound gives only ~27 passes per wave on this graph. So
+            # nothing here shows that the D = 5 spill of k_pfx_tiles<4> runs: it is unproven.
+            import torch
+            waves = 16 * torch.cuda.get_device_properties(0).multi_processor_count
+            passes = (tr[1]["active"] - g.nnz // 1024) / (128 // words) / waves
+            print(f"k_pfx_tiles K={K}: at least {passes:.1f} epilogue passes per wave")
+            assert passes >= 32, (K, words, tr[1], waves)
     for name in out:
         assert np.array_equal(out[name], out["plain"]), name
     sub = qs.subset(np.arange(0, K, 97))
