@@ -17,6 +17,9 @@
 //   --parent-out FILE  likewise the winning group's BFS parent row (n x int32: a source is its own
 //              parent, -1 unreached, else the first neighbour one level nearer in the row order
 //              of the graph the run used); may be given together with --dist-out
+//   --profile-out FILE  likewise one text line for the winning group, its level profile:
+//              "k reach ecc F h0 h1 ... h_ecc" (k the 0-based group index, h_L the vertices at
+//              distance exactly L); may be given together with the other two
 //   --spmd N   (N >= 1) single-process multi-GPU: N ranks as N threads of this process (thread r on device
 //              r % -gn), RCCL communicators from ncclCommInitAll when every rank owns a GPU
 //   --dist {auto,roundrobin,hybrid,hybrid-coded}  multi-rank decomposition (auto: hybrid when > 1
@@ -60,6 +63,7 @@ struct Args {
   bool host_csr = false;  // build the CSR of a graph file on the host (default: on the device)
   std::string dist_out;   // --dist-out FILE: the winning group's distance row (n x int32 LE)
   std::string parent_out;  // --parent-out FILE: the winning group's parent row (n x int32 LE)
+  std::string profile_out;  // --profile-out FILE: the winning group's level profile (one text line)
 };
 
 std::vector<std::string> split(const std::string& s, char d) {
@@ -667,6 +671,47 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
       if (!a.dist_out.empty()) write_row(a.dist_out, row, "--dist-out");
       if (want_parent) write_row(a.parent_out, prow, "--parent-out");
     }
+    // --profile-out: the winner's level profile, obtained the same way (one group through the
+    // per-group distance solver, or the CPU path): a first run for the eccentricity, a second
+    // with a column for every level
+    if (!a.profile_out.empty() && comm->rank() == 0 && K > 0 && minK >= 0) {
+      const int64_t woff[2] = {0, q.off[minK + 1] - q.off[minK]};
+      const int32_t* wids = q.ids.data() + q.off[minK];
+      int64_t Fw = 0, reach = 0;
+      int32_t ecc = -1;
+      std::vector<int64_t> hist;
+      std::unique_ptr<Solver> ds;
+      QuerySet w;
+      if (cpu) {
+        w.off.assign(woff, woff + 2);
+        w.ids.assign(wids, wids + woff[1]);
+      } else {
+        ds = make_dist_solver(dg);
+      }
+      auto profile = [&](int64_t* h, int64_t nbins) {
+        if (cpu) {
+          std::vector<int64_t> f;
+          CpuProfile p;
+          p.reach = &reach, p.ecc = &ecc, p.hist = h, p.nbins = nbins, p.ld = nbins;
+          cpu_msbfs_all(hg, w, f, nullptr, 1, nullptr, 0, nullptr, &p);
+          Fw = f[0];
+        } else {
+          ds->run_profile(1, woff, wids, &Fw, &reach, &ecc, h, nbins, nbins, nullptr, stream);
+        }
+      };
+      profile(nullptr, 1);
+      hist.assign((size_t)ecc + 2, 0);
+      profile(hist.data(), (int64_t)hist.size());
+      if (Fw != minF)
+        fail("--profile-out: the winner's run gives F " + std::to_string(Fw) + ", not its F " +
+             std::to_string(minF));
+      FILE* f = fopen(a.profile_out.c_str(), "w");
+      if (!f) fail("--profile-out: could not open " + a.profile_out);
+      fprintf(f, "%lld %lld %d %lld", (long long)minK, (long long)reach, (int)ecc, (long long)Fw);
+      for (int32_t L = 0; L <= ecc; ++L) fprintf(f, " %lld", (long long)hist[(size_t)L]);
+      fprintf(f, "\n");
+      if (fclose(f) != 0) fail("--profile-out: short write to " + a.profile_out);
+    }
     comm.reset();
   } catch (const std::exception& e) {
     fprintf(stderr, "msbfs: %s\n", e.what());
@@ -714,6 +759,7 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--host-csr")) a.host_csr = true;
     else if (!strcmp(argv[i], "--dist-out") && has) a.dist_out = argv[++i];
     else if (!strcmp(argv[i], "--parent-out") && has) a.parent_out = argv[++i];
+    else if (!strcmp(argv[i], "--profile-out") && has) a.profile_out = argv[++i];
   }
   int rc = 0;
   if (a.spmd >= 1) {

@@ -179,6 +179,18 @@ class Solver {
         (void)st, (void)stream;
     fail("parent output is not supported by this solver");
   }
+  // run() plus each group's level profile, all to host memory and each nullable: reach[k] =
+  // vertices with dist >= 0 (sources included), ecc[k] = the largest distance (-1 for a group
+  // without a valid source), hist[k * ld + L] (ld >= nbins >= 1) = vertices at distance exactly
+  // L for L < nbins - 1, at distance >= nbins - 1 in column nbins - 1; columns [nbins, ld) are
+  // never touched. reach and ecc are exact whatever nbins is. The traversal is run()'s own.
+  virtual void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                           int64_t* reach, int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld,
+                           RunStats* st, hipStream_t stream) {
+    (void)K, (void)qoff, (void)qids, (void)F, (void)reach, (void)ecc, (void)hist, (void)nbins,
+        (void)ld, (void)st, (void)stream;
+    fail("level profiles are not supported by this solver");
+  }
   // Groups one solver pass handles at once (bit-parallel: 64*W; per-group solvers run any
   // number in one call). Callers that overlap work between passes split runs at this size.
   virtual int64_t pass_groups() const { return INT64_MAX; }

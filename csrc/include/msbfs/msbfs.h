@@ -102,6 +102,12 @@ int msbfs_cpu_run_parents(int64_t n, const int64_t* rowptr, const int32_t* col, 
                           const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist,
                           int32_t* parent, int64_t ld, int nthreads);
 
+/* The same as msbfs_cpu_run plus each group's level profile (see msbfs_solver_run_profile: the
+ * same contract and argument checks; reach, ecc and hist each nullable). */
+int msbfs_cpu_run_profile(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
+                          const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
+                          int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, int nthreads);
+
 /* ---- device graphs ---- */
 int msbfs_graph_from_host_csr(int device, int64_t n, const int64_t* rowptr, const int32_t* col,
                               msbfs_graph* out);
@@ -201,6 +207,24 @@ int msbfs_solver_run_parents(msbfs_solver s, int64_t K, const int64_t* qoff, con
 int msbfs_solver_run_parents_host(msbfs_solver s, int64_t K, const int64_t* qoff,
                                   const int32_t* qids, int64_t* F, int32_t* dist_host,
                                   int32_t* parent_host, int64_t ld, msbfs_stats* st, void* stream);
+/* Level profile: F exactly as msbfs_solver_run returns it plus, per group and from every solver,
+ * all in host memory and each nullable:
+ *   reach[k]  int64  vertices with dist >= 0, the group's sources included
+ *   ecc[k]    int32  the largest distance (the k-center objective); -1 without a valid source
+ *   hist      int64  K x ld, ld >= nbins >= 1: hist[k*ld + L] = vertices at distance exactly L
+ *                    for L < nbins - 1; column nbins - 1 is the tail, vertices at distance
+ *                    >= nbins - 1; columns [nbins, ld) are never touched
+ * so sum_L hist[k][L] == reach[k], and where ecc[k] < nbins - 1 also sum_L L * hist[k][L] == F[k]
+ * and hist[k][ecc[k]] > 0 with nothing beyond it. hist[k][0] counts the distinct valid sources
+ * (duplicates and ids outside [0, n) do not count). reach and ecc are exact whatever nbins is.
+ * The bit-parallel solver runs the kernels and takes the decisions of msbfs_solver_run (no edge
+ * counting, leaf folding where that run folds, the device-driven level batches): the per-group
+ * counts of every level are kept where they are multiplied into F, a few atomics per group and
+ * level. The per-group solvers reduce their distance array once more after each group.
+ * Fails with a message for nbins < 1, or ld < nbins with a non-null hist. */
+int msbfs_solver_run_profile(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
+                             int64_t* F, int64_t* reach, int32_t* ecc, int64_t* hist,
+                             int64_t nbins, int64_t ld, msbfs_stats* st, void* stream);
 /* The degree from which the parent searches give a row to more than one lane group (a
  * constant of the build; the results do not depend on it). */
 int msbfs_parents_wide_degree(void);

@@ -596,6 +596,52 @@ int msbfs_cpu_run_parents(int64_t n, const int64_t* rowptr, const int32_t* col, 
   });
 }
 
+namespace {
+void check_profile_args(const char* who, int64_t K, const int64_t* qoff, const int32_t* qids,
+                        const int64_t* F, const int64_t* hist, int64_t nbins, int64_t ld) {
+  const std::string w(who);
+  if (K < 0 || (K > 0 && (!qoff || !F))) msbfs::fail(w + ": bad query set");
+  if (K > 0 && qoff[K] > qoff[0] && !qids) msbfs::fail(w + ": bad query set");
+  if (nbins < 1) msbfs::fail(w + ": nbins must be at least 1");
+  if (hist && ld < nbins) msbfs::fail(w + ": ld must be at least nbins");
+}
+}  // namespace
+
+int msbfs_solver_run_profile(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
+                             int64_t* F, int64_t* reach, int32_t* ecc, int64_t* hist,
+                             int64_t nbins, int64_t ld, msbfs_stats* st, void* stream) {
+  return guard([&] {
+    if (!s || !s->impl) msbfs::fail("null solver");
+    check_profile_args("run_profile", K, qoff, qids, F, hist, nbins, ld);
+    timed(s, stream, st, "solver run_profile", [&](msbfs::RunStats* rs, hipStream_t hs) {
+      if (K > 0) s->impl->run_profile(K, qoff, qids, F, reach, ecc, hist, nbins, ld, rs, hs);
+    });
+  });
+}
+
+int msbfs_cpu_run_profile(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
+                          const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
+                          int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, int nthreads) {
+  return guard([&] {
+    if (n < 0) msbfs::fail("cpu_run_profile: bad arguments");
+    check_profile_args("cpu_run_profile", K, qoff, qids, F, hist, nbins, ld);
+    if (K == 0) return;
+    msbfs::HostCsr g;
+    g.n = n;
+    g.rowptr.assign(rowptr, rowptr + n + 1);
+    g.col.assign(col, col + rowptr[n]);
+    g.m = rowptr[n] / 2;
+    msbfs::QuerySet q;
+    q.off.assign(qoff, qoff + K + 1);
+    q.ids.assign(qids, qids + qoff[K]);
+    std::vector<int64_t> f;
+    msbfs::CpuProfile p;
+    p.reach = reach, p.ecc = ecc, p.hist = hist, p.nbins = nbins, p.ld = ld;
+    msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, nullptr, 0, nullptr, &p);
+    std::memcpy(F, f.data(), K * sizeof(int64_t));
+  });
+}
+
 int msbfs_leaf_fold_on(int leaf_key, int relabelled, int rows_sorted, int count, int nparts,
                        int limited, int64_t n_core, int64_t n_eff) {
   msbfs::bp::LeafRun r;

@@ -60,9 +60,25 @@ void cpu_parent_row(const HostCsr& g, const int32_t* dist, int32_t* parent) {
   }
 }
 
+void cpu_profile_row(const int32_t* dist, int64_t n, int64_t k, const CpuProfile& p) {
+  int64_t* h = p.hist ? p.hist + k * p.ld : nullptr;
+  if (h) std::fill(h, h + p.nbins, int64_t{0});
+  int64_t reach = 0;
+  int32_t mx = -1;
+  for (int64_t v = 0; v < n; ++v) {
+    const int32_t d = dist[v];
+    if (d < 0) continue;
+    ++reach;
+    mx = std::max(mx, d);
+    if (h) ++h[std::min<int64_t>(d, p.nbins - 1)];
+  }
+  if (p.reach) p.reach[k] = reach;
+  if (p.ecc) p.ecc[k] = mx;
+}
+
 void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
                    std::vector<int64_t>* edges, int nthreads, int32_t* dist_out, int64_t ld,
-                   int32_t* parent_out) {
+                   int32_t* parent_out, const CpuProfile* profile) {
   const int64_t K = q.K();
   F.assign(K, 0);
   if (edges) edges->assign(K, 0);
@@ -81,6 +97,7 @@ void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
       // (the worker's distance array already is the row: -1 unreached, 0 the valid sources)
       if (dist_out) std::copy(dist.begin(), dist.begin() + g.n, dist_out + k * ld);
       if (parent_out) cpu_parent_row(g, dist.data(), parent_out + k * ld);
+      if (profile) cpu_profile_row(dist.data(), g.n, k, *profile);
     }
   };
   if (nthreads == 1) {

@@ -490,6 +490,27 @@ __device__ __forceinline__ bool bu_gate_open(const BuGate& g) {
   return !g.c || bu_gate_eval(*g.c, g.beta, g.alpha, g.first);
 }
 
+// The per-group level counts of a profile run (BitparSolver::run_profile), kept where they already
+// pass through on their way into F: hist[min(level, last) * 64 * W + group] += the level's count
+// (row `last` is the tail), unsigned and allowed to wrap until the batch ends (the leaf fold's
+// source corrections, k_leaf_sources). Those corrections touch levels 0-2 only and can take a
+// level's whole count away again, so rows 0 .. kProfExact - 1 always stand for one level each
+// (last >= kProfExact) and the eccentricity comes from them at the batch's end; far[group] = the
+// largest level >= kProfExact with a count, which nothing corrects. hist == nullptr (every other
+// run): no profile, one uniform branch per kernel.
+constexpr uint32_t kProfExact = 3;
+struct Prof {
+  unsigned long long* hist = nullptr;
+  uint32_t* far = nullptr;
+  uint32_t last = 0;
+  uint32_t level = 0;  // (k_level_reduce: the level of the launch; its weight may be 0)
+};
+__device__ __forceinline__ void prof_add(const Prof& p, int stride, int i, uint32_t level,
+                                         unsigned long long f) {
+  atomicAdd(&p.hist[(size_t)(level < p.last ? level : p.last) * stride + i], f);
+  if (level >= kProfExact) atomicMax(&p.far[i], level);
+}
+
 // Sum the level's slab rows: block (word, row-group); lane = group bit. F += level * count
 // (`level` is the weight: 0 for a level another rank of the hybrid mode accounts for),
 // alive_next |= groups with count > 0 (one ballot + one atomicOr per word per row-group).
@@ -499,7 +520,7 @@ __global__ __launch_bounds__(kBlock) void k_level_reduce(const uint32_t* slabF,
                                                          int rgroups, unsigned long long* F,
                                                          unsigned long long* E,
                                                          uint64_t* alive_next, uint32_t level,
-                                                         BuGate gate) {
+                                                         BuGate gate, Prof prof = Prof{}) {
   if (!bu_gate_open(gate)) return;  // (uniform: no barrier skipped by part of the block)
   __shared__ unsigned long long pf[kWaves][64], pe[kWaves][64];
   const int word = blockIdx.x % W, rg = blockIdx.x / W;
@@ -521,6 +542,7 @@ __global__ __launch_bounds__(kBlock) void k_level_reduce(const uint32_t* slabF,
       e += pe[w][lane];
     }
     if (f) atomicAdd(&F[i], f * level);
+    if (prof.hist && f) prof_add(prof, 64 * W, i, prof.level, f);
     if constexpr (COUNT) {
       if (e) atomicAdd(&E[i], e);
     }
@@ -539,7 +561,8 @@ __global__ __launch_bounds__(kBlock) void k_level_reduce_multi(const uint32_t* s
                                                                int nlev, int rgroups,
                                                                uint32_t level_first, int weight_l1,
                                                                unsigned long long* F,
-                                                               uint64_t* alive_next) {
+                                                               uint64_t* alive_next,
+                                                               Prof prof = Prof{}) {
   __shared__ uint32_t pl[kWaves][64];
   const int word = blockIdx.x % W, rg = blockIdx.x / W;
   const int lane = lane_id(), wv = threadIdx.x >> 6;
@@ -556,6 +579,7 @@ __global__ __launch_bounds__(kBlock) void k_level_reduce_multi(const uint32_t* s
       for (int w = 1; w < kWaves; ++w) f += pl[w][lane];
       const uint32_t lvl = level_first + (uint32_t)j;
       fw += (unsigned long long)f * ((lvl == 1 && !weight_l1) ? 0u : lvl);
+      if (prof.hist && f) prof_add(prof, 64 * W, i, lvl, f);
       const uint64_t m = __ballot(f != 0);
       if (lane == 0 && m) atomicOr((unsigned long long*)&alive_next[16 * j + word], m);
     }

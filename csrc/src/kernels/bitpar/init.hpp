@@ -62,7 +62,8 @@ __global__ __launch_bounds__(kBlock) void k_init(const int32_t* pv, const int32_
                                                  int32_t epoch, int32_t* fl, Ctr* ctr,
                                                  unsigned long long* E, uint64_t* alive,
                                                  uint32_t* anyvis, const int32_t* relabel,
-                                                 uint8_t* first = nullptr) {
+                                                 uint8_t* first = nullptr,
+                                                 Prof prof = Prof{}) {
   __shared__ LdsQueue q;
   __shared__ unsigned long long scratch[kWaves];
   q_init(q);
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(kBlock) void k_init(const int32_t* pv, const int32_
       const uint64_t old = atomicOr((unsigned long long*)&visA[(int64_t)v * W + word], bit);
       if (first) first[i] = !(old & bit);  // (leaf folding: the pair's first occurrence)
       if (!(old & bit)) {
+        if (prof.hist) atomicAdd(&prof.hist[k], 1ull);  // (a profile run's level 0)
         atomicOr((unsigned long long*)&visB[(int64_t)v * W + word], bit);
         atomicOr((unsigned long long*)&acc[(int64_t)v * W + word], bit);
         (void)alive;  // alive (groups with a valid source) is uploaded by the host

@@ -51,6 +51,7 @@ struct LeafArgs {
   const uint64_t* gmask;
   unsigned long long* F;
   uint32_t weight;  // level + 1
+  Prof prof;        // a profile run: the counts also go to level `weight` of its histogram
 };
 
 // parents per lane group and block iteration: the pass is a chain of dependent loads (list
@@ -119,7 +120,10 @@ template <int W>
 __device__ __forceinline__ void leaf_flush(const uint32_t* cnt, const LeafArgs& a) {
   __syncthreads();
   for (int i = threadIdx.x; i < 64 * W; i += kBlock)
-    if (cnt[i]) atomicAdd(&a.F[i], (unsigned long long)cnt[i] * a.weight);
+    if (cnt[i]) {
+      atomicAdd(&a.F[i], (unsigned long long)cnt[i] * a.weight);
+      if (a.prof.hist) prof_add(a.prof, 64 * W, i, a.weight, cnt[i]);
+    }
 }
 
 // The parents of the weight classes 1 .. kLeafClasses: list positions [0, npos), npos a multiple
@@ -251,7 +255,10 @@ __global__ __launch_bounds__(kBlock) void k_leaf_weigh_list(LeafArgs a, const in
 // Leaves that are sources (right after k_init; first[i] = pair i is the first (vertex, group)
 // pair of its kind, from k_init's atomicOr). vis = the rows after k_init: bit g of p's row says
 // that p is a source of g (read through anyvis: only sources are marked yet, and a lazy batch's
-// other rows are stale). F is unsigned and wraps; the batch's sum is right at its end.
+// other rows are stale). F is unsigned and wraps; the batch's sum is right at its end. A profile
+// run moves the same leaves between the levels of its histogram (k_init counted every source at
+// level 0): out of level 1 where p is a source, out of level 2 where it is not; the other end of
+// a two-vertex component comes in at level 1.
 template <int W>
 __global__ __launch_bounds__(kBlock) void k_leaf_sources(const int32_t* pv, const int32_t* pk,
                                                          const uint8_t* first, int64_t np,
@@ -259,7 +266,8 @@ __global__ __launch_bounds__(kBlock) void k_leaf_sources(const int32_t* pv, cons
                                                          const int64_t* rowptr, const int32_t* col,
                                                          const uint64_t* vis,
                                                          const uint32_t* anyvis, int32_t n_core,
-                                                         int32_t n_eff, unsigned long long* F) {
+                                                         int32_t n_eff, unsigned long long* F,
+                                                         Prof prof = Prof{}) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < np;
        i += (int64_t)gridDim.x * kBlock) {
     if (!first[i]) continue;
@@ -270,8 +278,13 @@ __global__ __launch_bounds__(kBlock) void k_leaf_sources(const int32_t* pv, cons
     const int32_t p = col[rowptr[v]];
     const bool psrc =
         any_visited(anyvis, p) && ((vis[(int64_t)p * W + (k >> 6)] >> (k & 63)) & 1ull);
-    if (p < n_core) atomicAdd(&F[k], 0ull - (psrc ? 1ull : 2ull));
-    else if (!psrc) atomicAdd(&F[k], 1ull);
+    if (p < n_core) {
+      atomicAdd(&F[k], 0ull - (psrc ? 1ull : 2ull));
+      if (prof.hist) atomicAdd(&prof.hist[(size_t)(psrc ? 1 : 2) * (64 * W) + k], 0ull - 1ull);
+    } else if (!psrc) {
+      atomicAdd(&F[k], 1ull);
+      if (prof.hist) atomicAdd(&prof.hist[(size_t)(64 * W) + k], 1ull);
+    }
   }
 }
 

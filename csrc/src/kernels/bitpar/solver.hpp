@@ -92,6 +92,11 @@ class BitparSolver final : public Solver {
   void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
                    int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
                    hipStream_t stream) override;
+  // run() plus each group's level profile (reach, eccentricity, vertices per level): the same
+  // kernels and decisions as run(); the counts are kept where they pass on their way into F
+  void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
+                   int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, RunStats* st,
+                   hipStream_t stream) override;
   void tune(const std::string& spec) override { tun_.parse(spec); }
   int64_t pass_groups() const override { return 64 * (int64_t)std::min(maxW_, opt.max_words); }
   // graph-derived tables and worst-case scratch, built before any timed run (bitpar_pull.hip)
@@ -538,6 +543,35 @@ class BitparSolver final : public Solver {
     MSBFS_HIP_CHECK(hipGetLastError());
   }
   std::unique_ptr<PinnedBuf> hbctr_;
+  // ---- level profiles (run_profile; Prof in bitpar/common.hpp)
+  // What a profile run asked for (host memory, whole run; a batch writes its groups' part)
+  struct ProfOut {
+    int64_t* reach = nullptr;
+    int32_t* ecc = nullptr;
+    int64_t* hist = nullptr;
+    int64_t nbins = 0, ld = 0;  // (nbins = 0: no histogram asked for)
+    bool on = false;
+  };
+  ProfOut pout_;
+  Prof prof_;  // the current batch's device counts; prof_.hist == nullptr outside a profile run
+  // far[64 * 16], then the histogram rows (rows x 64 * W of the batch); the batch's results
+  // (reach, ecc, the capped histogram group-major) on the device and in pinned memory
+  DevBuf prof_buf_, prof_res_;
+  std::unique_ptr<PinnedBuf> hprof_;
+  static constexpr int64_t kProfBins = 64;  // the bins prepare() sizes the buffers for
+  static int64_t prof_rows(int64_t nbins) { return std::max<int64_t>(nbins, kProfExact + 1); }
+  void prof_reserve(int w, int64_t nbins);
+  Prof prof_at(uint32_t level) const {
+    Prof p = prof_;
+    p.level = level;
+    return p;
+  }
+  template <int W>
+  void prof_begin(hipStream_t s);  // before start_batch: zeroed counts
+  // after the batch's last kernel: results -> pinned memory (enqueued; read_small waits) ...
+  template <int W>
+  void prof_finish(int64_t nb, hipStream_t s);
+  void prof_store(int64_t k0, int64_t nb);  // ... and from there to the caller's arrays
 };
 
 // explicit instantiation of a member template for every word count (W) and counting mode

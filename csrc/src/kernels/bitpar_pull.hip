@@ -129,6 +129,7 @@ void BitparSolver::prepare(hipStream_t s) {
   MSBFS_HIP_CHECK(hipMemGetInfo(&fr, &tot));
   if (db < fr / 8) desc_.ensure(db);  // (a graph filling HBM keeps the per-level sizing)
   pairs_.ensure((size_t)1 << 22);
+  prof_reserve(maxW_, kProfBins);  // (a profile run of the default bin count allocates nothing)
   (void)ne;
 }
 
@@ -604,7 +605,7 @@ void BitparSolver::bu_batch(Loop& S, RunStats* st, hipStream_t s) {
              &slots[i].actw2.v, gate, p);
     k_level_reduce<W, false><<<W * rg, kBlock, 0, s>>>(slabF<W>(0), slabE<W>(0), rows, rg, sm.F,
                                                        sm.E, aslot + 16 * (i + 1), level0 + 1 + i,
-                                                       gate);
+                                                       gate, prof_at(level0 + 1 + i));
     MSBFS_HIP_CHECK(hipGetLastError());
     // (a closed level appends nothing: its list is empty)
     if (S.fold) leaf_weigh<W>(O, alive, level0 + 2 + i, fl_out, 0, &slots[i + 1].fl2.v, s);
@@ -783,7 +784,7 @@ void BitparSolver::leaf_sources(const int32_t* pv, const int32_t* pk, int64_t np
   k_leaf_sources<W><<<cap(grid_for(np, kBlock)), kBlock, 0, s>>>(
       pv, pk, leaf_.first.as<uint8_t>(), np, g_.old2new, g_.rowptr, g_.col,
       vis_[0].as<uint64_t>(), anyvis_.as<uint32_t>(), (int32_t)leaf_.n_core, (int32_t)n_eff(),
-      sm.F);
+      sm.F, prof_);
   MSBFS_HIP_CHECK(hipGetLastError());
   // level 0: the parents among the sources (the first frontier list; its length is ctr's fl2)
   leaf_weigh<W>(vis_[0].as<uint64_t>(), sm.alive[0], 1, fl_[0].as<int32_t>(), 0,
@@ -798,7 +799,8 @@ void BitparSolver::leaf_weigh(const uint64_t* R, const uint64_t* alive, uint32_t
   const Small sm = small();
   const LeafArgs a{leaf_.plist.as<int32_t>(), leaf_.pw.as<int32_t>(), leaf_.pidx.as<int32_t>(),
                    leaf_.seen.as<uint64_t>(), leaf_.epoch.as<int32_t>(), leaf_epoch_, R,
-                   anyvis_.as<uint32_t>(), done_.as<uint32_t>(), alive, sm.gmask, sm.F, weight};
+                   anyvis_.as<uint32_t>(), done_.as<uint32_t>(), alive, sm.gmask, sm.F, weight,
+                   prof_};
   if (list) {
     // (a device-side length: these are the short lists of the late levels and the batches)
     const int g = cap(n_dev ? 64 : grid_for(n, kLeafU * L::TILE, 1024));

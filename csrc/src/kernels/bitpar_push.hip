@@ -148,7 +148,7 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
     if (pend < 0) return;
     k_level_reduce_multi<W><<<W * rg, kBlock, 0, s>>>(slabF_.as<uint32_t>(), grid, upto - pend,
                                                       rg, level0 + 1 + pend, S.weight_l1 ? 1 : 0,
-                                                      sm.F, aslot + 16 * (pend + 1));
+                                                      sm.F, aslot + 16 * (pend + 1), prof_);
     MSBFS_HIP_CHECK(hipGetLastError());
     aidx = upto;
     pend = -1;
@@ -223,7 +223,8 @@ void BitparSolver::td_batch(Loop& S, RunStats* st, hipStream_t s) {
     }
     k_level_reduce<W, COUNT><<<W * rg, kBlock, 0, s>>>(slabF_.as<uint32_t>(),
                                                        slabE_.as<unsigned long long>(), grid, rg,
-                                                       sm.F, sm.E, aslot + 16 * (i + 1), weight, BuGate{});
+                                                       sm.F, sm.E, aslot + 16 * (i + 1), weight, BuGate{},
+                                                       prof_at(level));
     MSBFS_HIP_CHECK(hipGetLastError());
     aidx = i + 1;
     S.fc ^= 1;

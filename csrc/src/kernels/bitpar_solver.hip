@@ -75,6 +75,99 @@ void BitparSolver::run(int64_t K, const int64_t* qoff, const int32_t* qids, int6
   if (st) st->builds += plen_builds_ - builds0;
 }
 
+// ---- level profiles -----------------------------------------------------------------------------
+// The end of a profile batch, one thread per group: reach = the sum of its histogram rows, the
+// eccentricity from far[] or, without a level >= kProfExact, the last of the exact rows with a
+// count (after the leaf fold's corrections), and the histogram capped at nbins columns (rows from
+// nbins - 1 on summed into the tail), group-major. res: reach[nb], ecc[nb] (as int64), then
+// nb x nbins counts.
+static __global__ __launch_bounds__(kBlock) void k_profile_finish(const Prof p, int rows,
+                                                                  int stride, int64_t nb,
+                                                                  int64_t nbins, long long* res) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nb) return;
+  long long* h = res + 2 * nb + k * nbins;
+  unsigned long long reach = 0, tail = 0;
+  for (int L = 0; L < rows; ++L) {
+    const unsigned long long c = p.hist[(size_t)L * stride + k];
+    reach += c;
+    if (L < nbins - 1) h[L] = (long long)c;
+    else tail += c;
+  }
+  if (nbins > 0) h[nbins - 1] = (long long)tail;
+  long long e = (long long)p.far[k];
+  if (e == 0) {
+    e = -1;
+    for (int L = 0; L < (int)kProfExact; ++L)
+      if (p.hist[(size_t)L * stride + k]) e = L;
+  }
+  res[k] = (long long)reach;
+  res[nb + k] = e;
+}
+
+void BitparSolver::prof_reserve(int w, int64_t nbins) {
+  const size_t g = (size_t)64 * w;
+  prof_buf_.ensure(64 * 16 * sizeof(uint32_t) + (size_t)prof_rows(nbins) * g * sizeof(uint64_t));
+  const size_t rb = (2 + (size_t)nbins) * g * sizeof(int64_t);
+  prof_res_.ensure(rb);
+  if (!hprof_ || hprof_->bytes < rb) hprof_ = std::make_unique<PinnedBuf>(rb);
+}
+
+template <int W>
+void BitparSolver::prof_begin(hipStream_t s) {
+  prof_ = Prof{};
+  if (!pout_.on) return;
+  prof_reserve(W, pout_.nbins);
+  const int64_t rows = prof_rows(pout_.nbins);
+  MSBFS_HIP_CHECK(hipMemsetAsync(
+      prof_buf_.p, 0, 64 * 16 * sizeof(uint32_t) + (size_t)rows * 64 * W * sizeof(uint64_t), s));
+  prof_.far = prof_buf_.as<uint32_t>();
+  prof_.hist = (unsigned long long*)(prof_.far + 64 * 16);
+  prof_.last = (uint32_t)(rows - 1);
+}
+
+template <int W>
+void BitparSolver::prof_finish(int64_t nb, hipStream_t s) {
+  if (!prof_.hist) return;
+  k_profile_finish<<<grid_for(nb, kBlock), kBlock, 0, s>>>(
+      prof_, (int)prof_.last + 1, 64 * W, nb, pout_.nbins, prof_res_.as<long long>());
+  MSBFS_HIP_CHECK(hipGetLastError());
+  MSBFS_HIP_CHECK(hipMemcpyAsync(hprof_->p, prof_res_.p,
+                                 (size_t)(2 + pout_.nbins) * nb * sizeof(int64_t),
+                                 hipMemcpyDeviceToHost, s));
+}
+
+void BitparSolver::prof_store(int64_t k0, int64_t nb) {
+  if (!prof_.hist) return;
+  const int64_t* r = hprof_->as<int64_t>();
+  for (int64_t k = 0; k < nb; ++k) {
+    if (pout_.reach) pout_.reach[k0 + k] = r[k];
+    if (pout_.ecc) pout_.ecc[k0 + k] = (int32_t)r[nb + k];
+    if (pout_.hist)
+      std::copy(r + 2 * nb + k * pout_.nbins, r + 2 * nb + (k + 1) * pout_.nbins,
+                pout_.hist + (k0 + k) * pout_.ld);
+  }
+  prof_ = Prof{};
+}
+
+void BitparSolver::run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
+                               int64_t* reach, int32_t* ecc, int64_t* hist, int64_t nbins,
+                               int64_t ld, RunStats* st, hipStream_t stream) {
+  if (nbins < 1) fail("run_profile: nbins must be at least 1");
+  if (hist && ld < nbins) fail("run_profile: ld must be at least nbins");
+  if (nbins > INT32_MAX / 2) fail("run_profile: too many bins");
+  // (cleared however the run ends: a later run() must count nothing of this)
+  struct Scope {
+    BitparSolver& b;
+    ~Scope() {
+      b.pout_ = ProfOut{};
+      b.prof_ = Prof{};
+    }
+  } scope{*this};
+  pout_ = ProfOut{reach, ecc, hist, hist ? nbins : 0, ld, true};
+  run(K, qoff, qids, F, nullptr, st, stream);
+}
+
 // ---- distance output (bitpar/record.hpp) --------------------------------------------------------
 // Level 0: the batch's (source, local group) pairs, original ids, range-checked by start_batch.
 // Duplicates store the same zero twice. out: row 0 = the batch's first group. parent != nullptr
@@ -258,7 +351,7 @@ void BitparSolver::start_batch(int64_t k0, int64_t nb, const int64_t* qoff, cons
         dpv, dpk, np, g_.rowptr, vis_[0].as<uint64_t>(), vis_[1].as<uint64_t>(),
         acc_[S.ac].as<uint64_t>(), stamp_.as<int32_t>(), epoch_, fl_[S.fc].as<int32_t>(),
         ctr_.as<Ctr>(), sm.E, sm.alive[0], anyvis_.as<uint32_t>(), g_.old2new,
-        S.fold ? leaf_.first.as<uint8_t>() : nullptr);
+        S.fold ? leaf_.first.as<uint8_t>() : nullptr, prof_);
     MSBFS_HIP_CHECK(hipGetLastError());
     if constexpr (!COUNT) {
       if (S.fold) leaf_sources<W>(dpv, dpk, np, s);  // (+ level 0's weighted count)
@@ -339,7 +432,8 @@ void BitparSolver::levels(Loop& S, RunStats* st, hipStream_t s) {
       const int rg = std::max(1, std::min(64, rows / 32));
       const uint32_t weight = (S.level == 1 && !S.weight_l1) ? 0u : S.level;
       k_level_reduce<W, COUNT><<<W * rg, kBlock, 0, s>>>(
-          slabF<W>(0), slabE<W>(0), rows, rg, sm.F, sm.E, sm.alive[S.alv ^ 1], weight, BuGate{});
+          slabF<W>(0), slabE<W>(0), rows, rg, sm.F, sm.E, sm.alive[S.alv ^ 1], weight, BuGate{},
+          prof_at(S.level));
       MSBFS_HIP_CHECK(hipGetLastError());
     }
     c = read_ctr(s);
@@ -410,6 +504,7 @@ void BitparSolver::batch_impl(int64_t k0, int64_t nb, const int64_t* qoff, const
   // lazy: no per-batch fill of vis_[0] (n_eff * 8W bytes, ~0.8 ms on RMAT-26); the edge-counting
   // pass re-reads both rows of every new vertex (k_count_frontier), so it keeps the fill
   S.lazy = tun_.lazy && !COUNT && !fused_batches<COUNT>();
+  prof_begin<W>(s);
   start_batch<W, COUNT>(k0, nb, qoff, qids, S, s);
   levels<W, COUNT>(S, st, s);
   // frontier is empty: accumulator entries were cleared by finalize / zero_acc
@@ -419,7 +514,9 @@ void BitparSolver::batch_impl(int64_t k0, int64_t nb, const int64_t* qoff, const
       if (st) st->leaf_folded = n_eff() - leaf_.n_core;
     }
   }
+  prof_finish<W>(nb, s);
   const unsigned long long* h = read_small(s);
+  prof_store(k0, nb);
   for (int64_t k = 0; k < nb; ++k) {
     Fout[k] = (int64_t)h[k];
     if (edges2) edges2[k] = (int64_t)h[64 * 16 + k];

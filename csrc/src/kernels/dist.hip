@@ -360,6 +360,95 @@ static void check_dist_out(const DeviceGraph& g, const int32_t* dist_dev, int64_
   if (ld < g.n) fail("run_dist: ld must be at least n");
 }
 
+// Level profile (Solver::run_profile): one pass over a group's distance array next to the F sum.
+// out[0] += reached vertices, out[1] = max(distance + 1), out[2 + b] += vertices in bin b =
+// min(distance, nbins - 1) (nbins = 0: no bins). The first kProfLds bins are privatised in LDS
+// (one global atomic per bin with a count per block); a vertex of a later bin (more than
+// kProfLds bins asked for, on a graph that deep) adds to global memory itself.
+constexpr int kProfLds = 2048;
+__global__ __launch_bounds__(kBlock) void k_profile_dist(const int32_t* dist, int64_t n,
+                                                         int64_t nbins, unsigned long long* out) {
+  __shared__ uint32_t bins[kProfLds];
+  __shared__ unsigned long long sr[kBlock / 64], sm[kBlock / 64];
+  const int nl = (int)(nbins < kProfLds ? nbins : kProfLds);
+  for (int i = threadIdx.x; i < nl; i += kBlock) bins[i] = 0;
+  __syncthreads();
+  unsigned long long reach = 0, mx = 0;
+  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n;
+       v += (int64_t)gridDim.x * kBlock) {
+    const int32_t d = dist[v];
+    if (d < 0) continue;
+    ++reach;
+    mx = mx > (unsigned long long)d + 1 ? mx : (unsigned long long)d + 1;
+    if (nbins > 0) {
+      const int64_t b = d < nbins - 1 ? d : nbins - 1;
+      if (b < nl) atomicAdd(&bins[b], 1u);
+      else atomicAdd(&out[2 + b], 1ull);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    reach += __shfl_xor(reach, off);
+    const unsigned long long o = __shfl_xor(mx, off);
+    mx = mx > o ? mx : o;
+  }
+  if (lane_id() == 0) {
+    sr[threadIdx.x >> 6] = reach;
+    sm[threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nl; i += kBlock)
+    if (bins[i]) atomicAdd(&out[2 + i], (unsigned long long)bins[i]);
+  if (threadIdx.x == 0) {
+    unsigned long long a = 0, b = 0;
+    for (int w = 0; w < kBlock / 64; ++w) {
+      a += sr[w];
+      b = b > sm[w] ? b : sm[w];
+    }
+    if (a) atomicAdd(&out[0], a);
+    if (b) atomicMax(&out[1], b);
+  }
+}
+// What a profile run asked for (host memory, see Solver::run_profile) and its device scratch;
+// row(): group k's profile from its finished distance array
+struct ProfileOut {
+  int64_t* reach = nullptr;
+  int32_t* ecc = nullptr;
+  int64_t* hist = nullptr;
+  int64_t nbins = 0, ld = 0;
+  bool on = false;
+  DevBuf buf;
+  std::vector<unsigned long long> h;
+  void begin(int64_t* r, int32_t* e, int64_t* hi, int64_t nb, int64_t l) {
+    if (nb < 1) fail("run_profile: nbins must be at least 1");
+    if (hi && l < nb) fail("run_profile: ld must be at least nbins");
+    reach = r, ecc = e, hist = hi, nbins = hi ? nb : 0, ld = l;
+    buf.ensure((size_t)(2 + nbins) * sizeof(unsigned long long));
+    h.resize((size_t)(2 + nbins));
+    on = true;
+  }
+  void row(const int32_t* dist, int64_t n, int64_t k, hipStream_t s) {
+    if (!on) return;
+    const size_t bytes = (size_t)(2 + nbins) * sizeof(unsigned long long);
+    MSBFS_HIP_CHECK(hipMemsetAsync(buf.p, 0, bytes, s));
+    if (n > 0)
+      k_profile_dist<<<grid_for(n, kBlock, 1024), kBlock, 0, s>>>(dist, n, nbins,
+                                                                  buf.as<unsigned long long>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+    MSBFS_HIP_CHECK(hipMemcpyAsync(h.data(), buf.p, bytes, hipMemcpyDeviceToHost, s));
+    MSBFS_HIP_CHECK(hipStreamSynchronize(s));
+    if (reach) reach[k] = (int64_t)h[0];
+    if (ecc) ecc[k] = (int32_t)((int64_t)h[1] - 1);
+    if (hist)
+      for (int64_t b = 0; b < nbins; ++b) hist[k * ld + b] = (int64_t)h[2 + b];
+  }
+};
+// (cleared however the run ends)
+struct ProfileScope {
+  ProfileOut& p;
+  ~ProfileScope() { p.on = false; }
+};
+
 // Parent output (Solver::run_parents): one group's row from the solver's own distance array,
 // over the internal ids i: out[user id of i] = -1 where unreached, the user's id itself for a
 // source, else the user's id of the first entry u of i's row with dist[u] == dist[i] - 1. Every
@@ -471,6 +560,13 @@ class DistSolver final : public Solver {
     check_dist_out(g_, dist_dev, ld);
     if (!parent_dev) fail("run_parents: no parent output");
     run_impl(K, qoff, qids, F, nullptr, dist_dev, parent_dev, ld, st, s);
+  }
+  void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
+                   int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, RunStats* st,
+                   hipStream_t s) override {
+    ProfileScope scope{prof_};
+    prof_.begin(reach, ecc, hist, nbins, ld);
+    run_impl(K, qoff, qids, F, nullptr, nullptr, nullptr, 0, st, s);
   }
 
  private:
@@ -614,6 +710,7 @@ class DistSolver final : public Solver {
       }
       if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
       if (pout) parent_row(g_, dist_.as<int32_t>(), n2o, pout + k * ld, s);
+      prof_.row(dist_.as<int32_t>(), n, k, s);
       visited_ = lo + nf;  // every visited vertex sits in ord[0, lo + nf)
       F[k] = Fk;
       if (edges2) edges2[k] = E2;
@@ -630,6 +727,7 @@ class DistSolver final : public Solver {
   DevBuf dist_, ord_, ul_[2], ulw_[2], offs_, scan_tmp_, ctr_, src_, slots_;
   size_t scan_bytes_ = 0;
   InverseMap inv_;
+  ProfileOut prof_;
   int64_t visited_ = 0;  // vertices the last group reached (ord[0, visited_) to reset)
   std::unique_ptr<PinnedBuf> hctr_, hslots_;
 };
@@ -660,6 +758,13 @@ class SweepSolver final : public Solver {
     check_dist_out(g_, dist_dev, ld);
     if (!parent_dev) fail("run_parents: no parent output");
     run_impl(K, qoff, qids, F, nullptr, dist_dev, parent_dev, ld, st, s);
+  }
+  void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
+                   int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, RunStats* st,
+                   hipStream_t s) override {
+    ProfileScope scope{prof_};
+    prof_.begin(reach, ecc, hist, nbins, ld);
+    run_impl(K, qoff, qids, F, nullptr, nullptr, nullptr, 0, st, s);
   }
 
  private:
@@ -708,10 +813,12 @@ class SweepSolver final : public Solver {
       if (edges2) edges2[k] = (int64_t)h[1];
       if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
       if (pout) parent_row(g_, dist_.as<int32_t>(), n2o, pout + k * ld, s);
+      prof_.row(dist_.as<int32_t>(), n, k, s);
     }
   }
 
   const DeviceGraph& g_;
+  ProfileOut prof_;
   DevBuf dist_, fl_, ctr_, red_, src_;
   InverseMap inv_;
   std::unique_ptr<PinnedBuf> hctr_;

@@ -567,6 +567,33 @@ int main(int argc, char** argv) {
       for (int64_t v = l1.n; v < ld; ++v) ok &= d1[k * ld + v] == 77;
     }
     CHECK(ok);
+    // ... and its level profiles (what msbfs_cpu_run_profile runs): threaded == serial == the
+    // distance rows' counts, the tail folded into the last of 3 columns, padding untouched
+    const int64_t nb = 3, pld = 5;
+    std::vector<int64_t> r1((size_t)K), r8((size_t)K), h1((size_t)(K * pld), -5), h8 = h1, Fp1, Fp8;
+    std::vector<int32_t> e1v((size_t)K), e8v((size_t)K);
+    CpuProfile p1, p8;
+    p1.reach = r1.data(), p1.ecc = e1v.data(), p1.hist = h1.data(), p1.nbins = nb, p1.ld = pld;
+    p8.reach = r8.data(), p8.ecc = e8v.data(), p8.hist = h8.data(), p8.nbins = nb, p8.ld = pld;
+    cpu_msbfs_all(l1, q, Fp1, nullptr, 1, nullptr, 0, nullptr, &p1);
+    cpu_msbfs_all(l1, q, Fp8, nullptr, T, nullptr, 0, nullptr, &p8);
+    CHECK(Fp1 == F1 && Fp8 == F1 && r1 == r8 && e1v == e8v && h1 == h8);
+    ok = true;
+    for (int64_t k = 0; k < K; ++k) {
+      int64_t cnt[3] = {0, 0, 0}, reach = 0;
+      int32_t mx = -1;
+      for (int64_t v = 0; v < l1.n; ++v) {
+        const int32_t d = d1[k * ld + v];
+        if (d < 0) continue;
+        ++reach;
+        mx = std::max(mx, d);
+        ++cnt[std::min<int32_t>(d, 2)];
+      }
+      ok &= reach == r1[k] && mx == e1v[k];
+      for (int b = 0; b < 3; ++b) ok &= h1[k * pld + b] == cnt[b];
+      for (int64_t b = nb; b < pld; ++b) ok &= h1[k * pld + b] == -5;
+    }
+    CHECK(ok);
   }
   unlink(gp.c_str());
   unlink((gp + ".csr").c_str());

@@ -22,6 +22,7 @@ __version__ = "0.1.0"
 from .ops import native  # noqa: E402
 from .ops.bfs import BfsResult, Solver, argmin_first, cpu_bfs, multi_source_bfs  # noqa: E402
 from .ops.bfs import nearest_source, path_to_set  # noqa: E402
+from .ops.bfs import harmonic, within  # noqa: E402
 from .models.graph import DeviceGraph, Graph  # noqa: E402
 from .models.queries import QuerySet  # noqa: E402
 from .models import generators  # noqa: E402

@@ -22,6 +22,7 @@ def main(argv=None) -> int:
     json_out = False
     dist_out = None  # --dist-out FILE: the winning group's distance row (n x int32 LE)
     parent_out = None  # --parent-out FILE: its BFS parent row (n x int32 LE)
+    profile_out = None  # --profile-out FILE: its level profile, "k reach ecc F h0 ... h_ecc"
     i = 1
     while i < len(argv):
         a = argv[i]
@@ -51,6 +52,8 @@ def main(argv=None) -> int:
             dist_out = argv[i + 1]; i += 1
         elif a == "--parent-out" and has:
             parent_out = argv[i + 1]; i += 1
+        elif a == "--profile-out" and has:
+            profile_out = argv[i + 1]; i += 1
         i += 1
     if cfg.num_gpu <= 0:
         print("msbfs: -gn must be >= 1", file=sys.stderr)
@@ -82,6 +85,11 @@ def main(argv=None) -> int:
                 row.astype("<i4").tofile(dist_out)
             if prow is not None:
                 prow.astype("<i4").tofile(parent_out)
+        if profile_out is not None:
+            line = eng.winner_profile(r)
+            if line is not None:
+                with open(profile_out, "w") as f:
+                    f.write(line + "\n")
     eng.close()
     D.shutdown(ctx)
     return 0

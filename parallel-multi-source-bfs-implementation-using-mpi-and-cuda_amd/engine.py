@@ -187,6 +187,26 @@ class Engine:
                                f"{int(res.F[0])}, not to its F {int(r.min_f)}")
         return res.dist[0], (res.parent[0] if parents else None)
 
+    def winner_profile(self, r: JobResult) -> Optional[str]:
+        """The winning group's level profile as the text line "k reach ecc F h0 h1 ... h_ecc"
+        (k the 0-based group index, h_L the vertices at distance exactly L); None when there is
+        no winner. Obtained the way winner_rows obtains its rows."""
+        if self.queries.K == 0 or r.min_k < 0:
+            return None
+        q = self.queries.subset(np.array([r.min_k], np.int64))
+        if self.on_gpu:
+            with Solver(self.dgraph, "dist", max_groups=1) as s:
+                res = s.profile(q, bins="all")
+        else:
+            g = self.graph_host if self.graph_host is not None else self.dgraph.download()
+            res = cpu_bfs(g, q, profile=True, bins="all")
+        if int(res.F[0]) != int(r.min_f):
+            raise RuntimeError(f"the winner's profile run gives F {int(res.F[0])}, not its F "
+                               f"{int(r.min_f)}")
+        e = int(res.ecc[0])
+        return " ".join(str(int(x)) for x in
+                        [r.min_k, res.reach[0], e, res.F[0], *res.hist[0, :e + 1]])
+
     def winner_distances(self, r: JobResult) -> Optional[np.ndarray]:
         """The winning group's distance row (see winner_rows)."""
         return self.winner_rows(r)[0]

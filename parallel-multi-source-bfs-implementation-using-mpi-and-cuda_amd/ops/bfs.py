@@ -35,6 +35,13 @@ class BfsResult:
     # int32[K, n] BFS parents (original vertex ids; a source is its own parent, -1 unreached) of
     # a parents() / parents=True call; None otherwise, and when they went to device buffers
     parent: Optional[np.ndarray] = None
+    # the level profile of a profile() / profile=True call (None otherwise): reach int64[K]
+    # (vertices reached, sources included), ecc int32[K] (largest distance, -1 for a group
+    # without a valid source), hist int64[K, bins] (vertices per distance; the last column is
+    # the tail: every vertex at distance >= bins - 1)
+    reach: Optional[np.ndarray] = None
+    ecc: Optional[np.ndarray] = None
+    hist: Optional[np.ndarray] = None
 
 
 def _host_dist_out(K: int, n: int, out: Optional[np.ndarray], ld: Optional[int]):
@@ -51,6 +58,29 @@ def _host_dist_out(K: int, n: int, out: Optional[np.ndarray], ld: Optional[int])
     if ld is not None and int(ld) != out.shape[1]:
         raise ValueError("ld must equal out.shape[1]")
     return out, out.shape[1]
+
+
+def _profile_call(K: int, bins, call) -> tuple:
+    """Run call(F, reach, ecc, hist, nbins) for `bins` columns; bins="all": 64 columns, and once
+    more with max(ecc) + 2 if a group reaches the tail (so that every level has its own column
+    and the tail column stays zero). Returns (F, reach, ecc, hist)."""
+    every = isinstance(bins, str)
+    if every and bins != "all":
+        raise ValueError('bins must be a positive integer or "all"')
+    nbins = 64 if every else int(bins)
+    if nbins < 1:
+        raise ValueError("bins must be at least 1")
+    while True:
+        F = np.zeros(K, dtype=np.int64)
+        reach = np.zeros(K, dtype=np.int64)
+        ecc = np.full(K, -1, dtype=np.int32)
+        hist = np.zeros((K, nbins), dtype=np.int64)
+        if K:
+            call(F, reach, ecc, hist, nbins)
+        if every and K and int(ecc.max()) >= nbins - 1:
+            nbins = int(ecc.max()) + 2
+            continue
+        return F, reach, ecc, hist
 
 
 class Solver:
@@ -186,6 +216,28 @@ class Solver:
                 native.ptr(Pm, C.c_int32), ld, C.byref(st), sp))
         return BfsResult(F, None, st.as_dict(), D[:, :n], Pm[:, :n])
 
+    def profile(self, queries: QuerySet, bins=64, stream: Optional[int] = None) -> BfsResult:
+        """F exactly as run() returns it plus each group's level profile, at the speed of run():
+        .reach[k] = vertices reached (sources included), .ecc[k] = largest distance (-1 for a
+        group without a valid source), .hist[k, L] = vertices at distance exactly L for
+        L < bins - 1, the last column counting every vertex at distance >= bins - 1. reach and
+        ecc are exact whatever `bins` is; hist[k].sum() == reach[k]. bins="all": 64 columns, and
+        a second run with max(ecc) + 2 columns if some group gets that far.
+        The bit-parallel solver runs the kernels of run() (leaf folding and the device-driven
+        level batches included) and keeps the per-level counts it multiplies into F."""
+        st = native.Stats()
+        sp = C.c_void_p(stream) if stream else None
+
+        def call(F, reach, ecc, hist, nbins):
+            native.check(native.lib().msbfs_solver_run_profile(
+                self._h, queries.K, native.ptr(queries.off, C.c_int64),
+                native.ptr(queries.ids, C.c_int32), native.ptr(F, C.c_int64),
+                native.ptr(reach, C.c_int64), native.ptr(ecc, C.c_int32),
+                native.ptr(hist, C.c_int64), nbins, nbins, C.byref(st), sp))
+
+        F, reach, ecc, hist = _profile_call(queries.K, bins, call)
+        return BfsResult(F, None, st.as_dict(), reach=reach, ecc=ecc, hist=hist)
+
     def level_trace(self) -> list:
         """Per-level records of the last run / hybrid phase (bit-parallel solver): batch, level,
         dir ('T' push / 'B' pull), kind (which pull a 'B' level ran: 't' tiles, 'p' per-vertex
@@ -312,12 +364,30 @@ class Solver:
 
 def cpu_bfs(graph: Graph, queries: QuerySet, threads: int = 0, count_edges: bool = False,
             distances: bool = False, out: Optional[np.ndarray] = None,
-            parents: bool = False) -> BfsResult:
+            parents: bool = False, profile: bool = False, bins=64) -> BfsResult:
     """Query-parallel host BFS (native C++ threads). distances=True: BfsResult.dist is the
     int32[K, n] distance matrix (see Solver.distances; `out` as there). parents=True: the
     distances plus BfsResult.parent, the int32[K, n] BFS parents (see Solver.parents; "first
-    neighbour" in the row order of `graph`)."""
+    neighbour" in the row order of `graph`). profile=True: BfsResult.reach, .ecc and .hist with
+    `bins` columns (see Solver.profile); not together with distances or parents."""
     K = queries.K
+    if profile:
+        if distances or parents:
+            raise ValueError("profile=True does not combine with distances or parents")
+
+        def call(F, reach, ecc, hist, nbins):
+            native.check(native.lib().msbfs_cpu_run_profile(
+                graph.n, native.ptr(graph.rowptr, C.c_int64), native.ptr(graph.col, C.c_int32),
+                K, native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32),
+                native.ptr(F, C.c_int64), native.ptr(reach, C.c_int64),
+                native.ptr(ecc, C.c_int32), native.ptr(hist, C.c_int64), nbins, nbins,
+                int(threads)))
+
+        F, reach, ecc, hist = _profile_call(K, bins, call)
+        E = None
+        if count_edges:
+            E = cpu_bfs(graph, queries, threads, count_edges=True).edges
+        return BfsResult(F, E, {}, reach=reach, ecc=ecc, hist=hist)
     F = np.zeros(K, dtype=np.int64)
     E = np.zeros(K, dtype=np.int64) if count_edges else None
     if distances or parents:
@@ -346,21 +416,28 @@ def cpu_bfs(graph: Graph, queries: QuerySet, threads: int = 0, count_edges: bool
 
 def multi_source_bfs(graph: Union[Graph, DeviceGraph], queries: QuerySet, algo: str = "auto",
                      device: int = 0, count_edges: bool = False, distances: bool = False,
-                     parents: bool = False, **opts) -> BfsResult:
+                     parents: bool = False, profile: bool = False, bins=64,
+                     **opts) -> BfsResult:
     """One-shot convenience wrapper (creates and frees a Solver). distances=True: the result
     also carries the int32[K, n] distance matrix (Solver.distances); parents=True: that and the
-    BFS parent matrix (Solver.parents). The traversed-edge counts then come from a second,
-    plain run when count_edges is set too."""
+    BFS parent matrix (Solver.parents); profile=True (not with either): the level profile with
+    `bins` columns (Solver.profile). The traversed-edge counts then come from a second, plain
+    run when count_edges is set too."""
+    if profile and (distances or parents):
+        raise ValueError("profile=True does not combine with distances or parents")
     if algo == "cpu":
         if isinstance(graph, DeviceGraph):
             graph = graph.download()
         return cpu_bfs(graph, queries, count_edges=count_edges, distances=distances,
-                       parents=parents)
+                       parents=parents, profile=profile, bins=bins)
     dg = graph if isinstance(graph, DeviceGraph) else DeviceGraph.from_host(graph, device)
     with Solver(dg, algo, max_groups=max(1, queries.K), **opts) as s:
-        if not distances and not parents:
+        if not distances and not parents and not profile:
             return s.run(queries, count_edges=count_edges)
-        r = s.parents(queries) if parents else s.distances(queries)
+        if profile:
+            r = s.profile(queries, bins=bins)
+        else:
+            r = s.parents(queries) if parents else s.distances(queries)
         if count_edges:
             r.edges = s.run(queries, count_edges=True).edges
         return r
@@ -398,6 +475,36 @@ def nearest_source(parent: np.ndarray) -> np.ndarray:
         cur = nxt
     out = np.where(reached, cur, -1).astype(np.int32)
     return out if np.ndim(parent) == 2 else out[0]
+
+
+def harmonic(hist: np.ndarray) -> np.ndarray:
+    """Harmonic closeness of every group from its level histogram (BfsResult.hist):
+    sum over L >= 1 of hist[:, L] / L, float64[K] (a float for one row). The tail column mixes
+    levels, so a non-zero tail of a histogram with more than one column raises ValueError (ask
+    for more bins, or bins="all")."""
+    H = np.array(hist, dtype=np.int64, ndmin=2)
+    nb = H.shape[1]
+    if nb > 1 and np.any(H[:, nb - 1] != 0):
+        raise ValueError("the tail bucket is not empty: the histogram has too few bins")
+    out = (H[:, 1:] / np.arange(1, max(nb, 1), dtype=np.float64)).sum(axis=1) if nb > 1 \
+        else np.zeros(H.shape[0], dtype=np.float64)
+    return out if np.ndim(hist) == 2 else float(out[0])
+
+
+def within(hist: np.ndarray, r: int) -> np.ndarray:
+    """Vertices within r hops of every group (its sources included) from its level histogram:
+    int64[K] (an int for one row). r must lie below the tail column, whose vertices have no
+    single distance, unless that column is zero (then every reached vertex is counted)."""
+    H = np.array(hist, dtype=np.int64, ndmin=2)
+    nb = H.shape[1]
+    r = int(r)
+    if r < 0:
+        out = np.zeros(H.shape[0], dtype=np.int64)
+    else:
+        if r >= nb - 1 and np.any(H[:, nb - 1] != 0) and nb > 0:
+            raise ValueError("r reaches the tail bucket: the histogram has too few bins")
+        out = H[:, :min(r, nb - 1) + 1].sum(axis=1)
+    return out if np.ndim(hist) == 2 else int(out[0])
 
 
 def argmin_first(F: np.ndarray) -> int:

@@ -123,6 +123,10 @@ def _sig(lib):
         "msbfs_parents_wide_degree": (C.c_int, []),
         "msbfs_cpu_run_parents": (C.c_int, [C.c_int64, i64p, i32p, C.c_int64, i64p, i32p, i64p,
                                             i32p, i32p, C.c_int64, C.c_int]),
+        "msbfs_solver_run_profile": (C.c_int, [vp, C.c_int64, i64p, i32p, i64p, i64p, i32p, i64p,
+                                               C.c_int64, C.c_int64, P(Stats), vp]),
+        "msbfs_cpu_run_profile": (C.c_int, [C.c_int64, i64p, i32p, C.c_int64, i64p, i32p, i64p,
+                                            i64p, i32p, i64p, C.c_int64, C.c_int64, C.c_int]),
         "msbfs_solver_free": (None, [vp]),
         "msbfs_solver_levels": (C.c_int64, [vp, P(Level), C.c_int64]),
         "msbfs_argmin": (C.c_int64, [i64p, C.c_int64]),

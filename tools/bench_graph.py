@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--force-dir", type=int, default=0)
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default RCCL)")
     ap.add_argument("--trace-out", default="", help="write rank 0's per-level records (JSON)")
+    ap.add_argument("--profile", type=int, default=0,
+                    help="N > 0: time run() against profile(bins=64), alternated N times each "
+                         "(\"ab\" in the JSON line: ms per call, in order)")
     args = ap.parse_args()
     import torch
     import msbfs
@@ -84,6 +87,21 @@ def main():
         torch.cuda.synchronize(dev)
         D.barrier(ctx)
         dt = D.allreduce_max((time.perf_counter() - t1) / max(1, args.steps), ctx)
+        ab = None
+        if args.profile > 0:
+            # run() against profile(), alternated; the profile's F must be run()'s
+            ab = {"run_ms": [], "profile_ms": []}
+            s.profile(local)  # (untimed: its first call)
+            for _ in range(args.profile):
+                for key, fn in (("run_ms", s.run), ("profile_ms", s.profile)):
+                    torch.cuda.synchronize(dev)
+                    ta = time.perf_counter()
+                    rr = fn(local)
+                    torch.cuda.synchronize(dev)
+                    ab[key].append(round((time.perf_counter() - ta) * 1e3, 3))
+                    assert np.array_equal(rr.F, r0.F), key
+            ab["reach_min_max"] = [int(rr.reach.min()), int(rr.reach.max())] if local.K else []
+            ab["ecc_max"] = int(rr.ecc.max()) if local.K else -1
         # (untimed: solver time only; with --steps 0 the answer comes from the counting pass)
         min_k, min_f = D.packed_argmin(r.F, idx, qs.K, ctx)
         if args.verify and local.K:  # (untimed) the counting pass and the last timed run
@@ -99,7 +117,8 @@ def main():
         print(json.dumps({"graph": args.graph, "algo": args.algo, "n": g.n, "m": g.m,
                           "K": qs.K, "n_gpus": ctx.world, "ms": dt * 1e3, "teps": edges / dt if dt > 0 else 0.0,
                           "traversed_edges": edges, "stats": r.stats, "prep_s": round(prep, 3),
-                          "min_k": int(min_k) + 1, "min_f": int(min_f)}), flush=True)
+                          "min_k": int(min_k) + 1, "min_f": int(min_f),
+                          **({"ab": ab} if ab else {})}), flush=True)
     D.shutdown(ctx)
 
 
