@@ -422,7 +422,8 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
     RunStats rs;
     if (hybrid && a.json && nlocal) {  // TEPS numerator: untimed counting pass of the own groups
       std::vector<int64_t> Ft(nlocal);
-      solver->run(nlocal, local.off.data(), local.ids.data(), Ft.data(), E2.data(), nullptr, stream);
+      solver->run(nlocal, local.off.data(), local.ids.data(), Ft.data(), E2.data(), {}, nullptr,
+                  stream);
     }
     // Round robin runs its groups in passes of the solver's width (64*W groups); each pass's
     // packed key goes into an asynchronous MIN all-reduce on the communicator's own stream
@@ -553,7 +554,7 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
           const int64_t i1 = std::min<int64_t>(i0 + pass, nlocal);
           if (i1 > i0)
             solver->run(i1 - i0, local.off.data() + i0, local.ids.data(), F.data() + i0,
-                        a.json ? E2.data() + i0 : nullptr, &rs, stream);
+                        a.json ? E2.data() + i0 : nullptr, {}, &rs, stream);
           if (b + 1 == npass) maybe_inject("compute", comm->rank());
           if (pending == nslots) drain();
           comm->allreduce_min_u64_async(pack(i0, i1), pending++);
@@ -623,34 +624,47 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
       }
     }
     solver.reset();
-    // --dist-out: after the report (outside the computation boundary) rank 0 computes the
-    // winning group's distance row, with the per-group distance solver for one group (CPU path
-    // for --algo cpu), and writes n little-endian int32 (original vertex ids, -1 unreached)
-    // --parent-out: the same run also gives the winner's parent row (run_parents)
+    // After the report (outside the computation boundary) rank 0 runs the winning group again for
+    // --dist-out / --parent-out / --profile-out: one group through the per-group distance solver
+    // (the CPU path for --algo cpu). winner_run: the winner's F, with what `out` asks for
+    // (matrices in device memory on the device path)
     const bool want_parent = !a.parent_out.empty();
-    if ((!a.dist_out.empty() || want_parent) && comm->rank() == 0 && K > 0 && minK >= 0) {
-      std::vector<int32_t> row((size_t)std::max<int64_t>(nverts, 1), -1);
-      std::vector<int32_t> prow(want_parent ? row.size() : 0, -1);
-      const int64_t woff[2] = {0, q.off[minK + 1] - q.off[minK]};
-      const int32_t* wids = q.ids.data() + q.off[minK];
+    const bool want_rows = !a.dist_out.empty() || want_parent;
+    const bool winner = (want_rows || !a.profile_out.empty()) && comm->rank() == 0 && K > 0 && minK >= 0;
+    const int64_t woff[2] = {0, winner ? q.off[minK + 1] - q.off[minK] : 0};
+    const int32_t* wids = winner ? q.ids.data() + q.off[minK] : nullptr;
+    QuerySet w;
+    std::unique_ptr<Solver> ds;
+    if (winner && cpu) {
+      w.off.assign(woff, woff + 2);
+      w.ids.assign(wids, wids + woff[1]);
+    } else if (winner) {
+      ds = make_dist_solver(dg);
+    }
+    auto winner_run = [&](const RunOutputs& out) {
       int64_t Fw = 0;
       if (cpu) {
-        QuerySet w;
-        w.off.assign(woff, woff + 2);
-        w.ids.assign(wids, wids + woff[1]);
         std::vector<int64_t> f;
-        cpu_msbfs_all(hg, w, f, nullptr, 1, row.data(), nverts,
-                      want_parent ? prow.data() : nullptr);
+        cpu_msbfs_all(hg, w, f, nullptr, 1, out);
         Fw = f[0];
       } else {
-        std::unique_ptr<Solver> ds = make_dist_solver(dg);
-        const size_t rb = (size_t)std::max<int64_t>(nverts, 1) * sizeof(int32_t);
-        DevBuf drow(rb), dprow(want_parent ? rb : 0);
-        if (want_parent)
-          ds->run_parents(1, woff, wids, &Fw, drow.as<int32_t>(), dprow.as<int32_t>(), nverts,
-                          nullptr, stream);
-        else
-          ds->run_dist(1, woff, wids, &Fw, drow.as<int32_t>(), nverts, nullptr, stream);
+        ds->run(1, woff, wids, &Fw, nullptr, out, nullptr, stream);
+      }
+      return Fw;
+    };
+    // --dist-out: the winner's distance row, n little-endian int32 (original vertex ids, -1
+    // unreached); --parent-out: the same run also gives its parent row
+    if (winner && want_rows) {
+      std::vector<int32_t> row((size_t)std::max<int64_t>(nverts, 1), -1);
+      std::vector<int32_t> prow(want_parent ? row.size() : 0, -1);
+      DevBuf drow, dprow;
+      if (!cpu) drow.alloc(row.size() * sizeof(int32_t));
+      if (!cpu && want_parent) dprow.alloc(row.size() * sizeof(int32_t));
+      int32_t* const d = cpu ? row.data() : drow.as<int32_t>();
+      int32_t* const p = cpu ? prow.data() : dprow.as<int32_t>();
+      const int64_t Fw = winner_run(want_parent ? RunOutputs::parents(d, p, nverts)
+                                                : RunOutputs::distances(d, nverts));
+      if (!cpu) {
         MSBFS_HIP_CHECK(hipMemcpyAsync(row.data(), drow.p, (size_t)nverts * sizeof(int32_t),
                                        hipMemcpyDeviceToHost, stream));
         if (want_parent)
@@ -671,37 +685,15 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
       if (!a.dist_out.empty()) write_row(a.dist_out, row, "--dist-out");
       if (want_parent) write_row(a.parent_out, prow, "--parent-out");
     }
-    // --profile-out: the winner's level profile, obtained the same way (one group through the
-    // per-group distance solver, or the CPU path): a first run for the eccentricity, a second
-    // with a column for every level
-    if (!a.profile_out.empty() && comm->rank() == 0 && K > 0 && minK >= 0) {
-      const int64_t woff[2] = {0, q.off[minK + 1] - q.off[minK]};
-      const int32_t* wids = q.ids.data() + q.off[minK];
-      int64_t Fw = 0, reach = 0;
+    // --profile-out: the winner's level profile: a first run for the eccentricity, a second with
+    // a column for every level
+    if (winner && !a.profile_out.empty()) {
+      int64_t reach = 0;
       int32_t ecc = -1;
-      std::vector<int64_t> hist;
-      std::unique_ptr<Solver> ds;
-      QuerySet w;
-      if (cpu) {
-        w.off.assign(woff, woff + 2);
-        w.ids.assign(wids, wids + woff[1]);
-      } else {
-        ds = make_dist_solver(dg);
-      }
-      auto profile = [&](int64_t* h, int64_t nbins) {
-        if (cpu) {
-          std::vector<int64_t> f;
-          CpuProfile p;
-          p.reach = &reach, p.ecc = &ecc, p.hist = h, p.nbins = nbins, p.ld = nbins;
-          cpu_msbfs_all(hg, w, f, nullptr, 1, nullptr, 0, nullptr, &p);
-          Fw = f[0];
-        } else {
-          ds->run_profile(1, woff, wids, &Fw, &reach, &ecc, h, nbins, nbins, nullptr, stream);
-        }
-      };
-      profile(nullptr, 1);
-      hist.assign((size_t)ecc + 2, 0);
-      profile(hist.data(), (int64_t)hist.size());
+      winner_run(RunOutputs::profile(&reach, &ecc, nullptr, 1, 1));
+      std::vector<int64_t> hist((size_t)ecc + 2, 0);
+      const int64_t nbins = (int64_t)hist.size();
+      const int64_t Fw = winner_run(RunOutputs::profile(&reach, &ecc, hist.data(), nbins, nbins));
       if (Fw != minF)
         fail("--profile-out: the winner's run gives F " + std::to_string(Fw) + ", not its F " +
              std::to_string(minF));
@@ -712,6 +704,7 @@ int rank_main(Args a, std::unique_ptr<Comm> world, bool upgraded) {
       fprintf(f, "\n");
       if (fclose(f) != 0) fail("--profile-out: short write to " + a.profile_out);
     }
+    ds.reset();
     comm.reset();
   } catch (const std::exception& e) {
     fprintf(stderr, "msbfs: %s\n", e.what());

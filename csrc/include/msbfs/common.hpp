@@ -25,6 +25,82 @@ struct Error : std::runtime_error {
 
 [[noreturn]] void fail(const std::string& msg);
 
+// What a run returns next to F (and the edge counts): nothing, the distances, the distances and
+// the parents, or the level profiles. One description for every solver and for the CPU oracle
+// (Solver::run, cpu_msbfs_all); pointers and sizes only, nothing is owned.
+struct RunOutputs {
+  enum Kind { kPlain, kDist, kParents, kProfile };
+  // dist[k * ld + v] (K x ld int32, ld >= n; device memory for a device solver, host memory for
+  // the CPU oracle) = BFS level of vertex v (the user's id, also on relabelled graphs) from group
+  // k, 0 for its valid sources, -1 where unreached. Columns [0, n) of every row are written (a
+  // group without a valid source gives a row of -1), columns [n, ld) are never touched. The
+  // reached (>= 0) entries of row k sum to F[k].
+  int32_t* dist = nullptr;
+  // parent[k * ld + v] (laid out and padded like dist) = v for the valid sources of group k, -1
+  // where unreached, otherwise the user's id of the first neighbour u, in the order of v's row
+  // in the graph (a device graph's internal ids), with dist[k][u] == dist[k][v] - 1. Every
+  // solver on one DeviceGraph returns the same matrix.
+  int32_t* parent = nullptr;
+  int64_t ld = 0;
+  // Each group's level profile, all in host memory and each nullable: reach[k] = vertices with
+  // dist >= 0 (sources included), ecc[k] = the largest distance (-1 for a group without a valid
+  // source), hist[k * hist_ld + L] (hist_ld >= nbins >= 1) = vertices at distance exactly L for
+  // L < nbins - 1, at distance >= nbins - 1 in column nbins - 1; columns [nbins, hist_ld) are
+  // never touched. reach and ecc are exact whatever nbins is. The traversal is a plain run's own.
+  int64_t* reach = nullptr;
+  int32_t* ecc = nullptr;
+  int64_t* hist = nullptr;
+  int64_t nbins = 0, hist_ld = 0;
+  // What the caller asked for (the makers below set it). The fields alone do not say: all three
+  // arrays of a profile may be null, and a matrix that is missing is an error, not a plain run.
+  Kind asked = kPlain;
+
+  static RunOutputs distances(int32_t* dist, int64_t ld) {
+    RunOutputs o;
+    o.dist = dist, o.ld = ld, o.asked = kDist;
+    return o;
+  }
+  static RunOutputs parents(int32_t* dist, int32_t* parent, int64_t ld) {
+    RunOutputs o;
+    o.dist = dist, o.parent = parent, o.ld = ld, o.asked = kParents;
+    return o;
+  }
+  static RunOutputs profile(int64_t* reach, int32_t* ecc, int64_t* hist, int64_t nbins,
+                            int64_t hist_ld) {
+    RunOutputs o;
+    o.reach = reach, o.ecc = ecc, o.hist = hist, o.nbins = nbins, o.hist_ld = hist_ld;
+    o.asked = kProfile;
+    return o;
+  }
+
+  // One of the four shapes; edges: the run also returns edge counts (plain runs only). Fields of
+  // another shape than the one asked for are an error: no combination of outputs is supported.
+  Kind kind(bool edges = false) const {
+    const bool matrix = dist || parent, prof = reach || ecc || hist;
+    if ((asked == kProfile ? matrix : prof) || (asked == kPlain && matrix) ||
+        (asked == kDist && parent) || (asked != kPlain && edges))
+      fail("run: unsupported combination of outputs");
+    return asked;
+  }
+  // The argument checks of every entry point, for a graph of n vertices and K groups (K = 0: no
+  // rows, the matrices may be missing). who: the caller's name in the message (default: the
+  // device entry point's).
+  void validate(int64_t n, const char* who = nullptr, int64_t K = 1) const {
+    const Kind k = kind();
+    const std::string w(who ? who : k == kProfile ? "run_profile" : "run_dist");
+    if (k == kDist || k == kParents) {
+      if (K > 0 && !dist) fail(w + ": no distance output");
+      if (ld < n) fail(w + ": ld must be at least n");
+      if (k == kParents && K > 0 && !parent) fail("run_parents: no parent output");
+    } else if (k == kProfile) {
+      if (nbins < 1) fail(w + ": nbins must be at least 1");
+      if (hist && hist_ld < nbins) fail(w + ": ld must be at least nbins");
+    }
+  }
+  // histogram columns that are counted at all (none without a histogram array)
+  int64_t bins() const { return hist ? nbins : 0; }
+};
+
 // ---------------------------------------------------------------------------------------
 // Counter-based RNG (splitmix64 finaliser). Identical on host and device so that a graph
 // generated on the GPU is edge-for-edge the graph the host generator writes to a .bin file.

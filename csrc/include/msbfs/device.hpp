@@ -136,7 +136,7 @@ struct InverseMap {
 
 // ---- solvers ---------------------------------------------------------------------------------
 constexpr int kDefaultWideDegree = 32;
-// Parent output (Solver::run_parents): rows of at least this many entries are searched by more
+// Parent output (RunOutputs::parent): rows of at least this many entries are searched by more
 // than one lane group (bit-parallel: a block per vertex, per-group solvers: a wave). A constant,
 // not a tuning key: the result does not depend on it. msbfs_parents_wide_degree() returns it.
 constexpr int kParentsWideDegree = 256;
@@ -154,43 +154,12 @@ struct SolverOptions {
 class Solver {
  public:
   virtual ~Solver() = default;
-  // Runs groups [0,K) of a packed query set; F[k] and (optionally) edges2[k] (= sum of degrees
-  // of reached vertices, i.e. 2x the Graph500 traversed-edge count) are written to host memory.
+  // Runs groups [0,K) of a packed query set; F[k] and (optionally, plain runs only) edges2[k]
+  // (= sum of degrees of reached vertices, i.e. 2x the Graph500 traversed-edge count) are
+  // written to host memory, and what `out` asks for (see RunOutputs; its matrices are device
+  // memory) where it says.
   virtual void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                   int64_t* edges2, RunStats* st, hipStream_t stream) = 0;
-  // run() plus the per-vertex distances: dist_dev[k * ld + v] (device memory, K x ld int32,
-  // ld >= n) = BFS level of vertex v (the user's id, also on relabelled graphs) from group k, 0
-  // for its valid sources, -1 where unreached. Columns [0, n) of every row are written (a group
-  // without a valid source gives a row of -1), columns [n, ld) are never touched.
-  // The reached (>= 0) entries of row k sum to F[k].
-  virtual void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                        int32_t* dist_dev, int64_t ld, RunStats* st, hipStream_t stream) {
-    (void)K, (void)qoff, (void)qids, (void)F, (void)dist_dev, (void)ld, (void)st, (void)stream;
-    fail("distance output is not supported by this solver");
-  }
-  // run_dist() plus the BFS parents: parent_dev[k * ld + v] (laid out and padded like dist_dev)
-  // = v for the valid sources of group k, -1 where unreached, otherwise the user's id of the
-  // first neighbour u, in the order of v's row in the device graph (internal ids), with
-  // dist[k][u] == dist[k][v] - 1. Every solver on one DeviceGraph returns the same matrix.
-  virtual void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                           int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
-                           hipStream_t stream) {
-    (void)K, (void)qoff, (void)qids, (void)F, (void)dist_dev, (void)parent_dev, (void)ld,
-        (void)st, (void)stream;
-    fail("parent output is not supported by this solver");
-  }
-  // run() plus each group's level profile, all to host memory and each nullable: reach[k] =
-  // vertices with dist >= 0 (sources included), ecc[k] = the largest distance (-1 for a group
-  // without a valid source), hist[k * ld + L] (ld >= nbins >= 1) = vertices at distance exactly
-  // L for L < nbins - 1, at distance >= nbins - 1 in column nbins - 1; columns [nbins, ld) are
-  // never touched. reach and ecc are exact whatever nbins is. The traversal is run()'s own.
-  virtual void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                           int64_t* reach, int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld,
-                           RunStats* st, hipStream_t stream) {
-    (void)K, (void)qoff, (void)qids, (void)F, (void)reach, (void)ecc, (void)hist, (void)nbins,
-        (void)ld, (void)st, (void)stream;
-    fail("level profiles are not supported by this solver");
-  }
+                   int64_t* edges2, const RunOutputs& out, RunStats* st, hipStream_t stream) = 0;
   // Groups one solver pass handles at once (bit-parallel: 64*W; per-group solvers run any
   // number in one call). Callers that overlap work between passes split runs at this size.
   virtual int64_t pass_groups() const { return INT64_MAX; }

@@ -98,24 +98,15 @@ int64_t cpu_msbfs_F(const HostCsr& g, const int32_t* src, int64_t nsrc, std::vec
 // where dist[v] == 0, -1 where unreached, else the first entry u of v's row with dist[u] ==
 // dist[v] - 1 (the row order decides, not which vertex discovered v). Writes parent[0, n).
 void cpu_parent_row(const HostCsr& g, const int32_t* dist, int32_t* parent);
-// Level profile of the groups (msbfs_cpu_run_profile): each array nullable; reach[k] = reached
-// vertices, ecc[k] = largest distance (-1: no valid source), hist[k * ld + b] = vertices in bin
-// b = min(distance, nbins - 1), columns [nbins, ld) untouched (ld >= nbins >= 1).
-struct CpuProfile {
-  int64_t* reach = nullptr;
-  int32_t* ecc = nullptr;
-  int64_t* hist = nullptr;
-  int64_t nbins = 1, ld = 1;
-};
-// One group's profile from its distance array (as cpu_msbfs_F leaves it), into row k of p
-void cpu_profile_row(const int32_t* dist, int64_t n, int64_t k, const CpuProfile& p);
-// All groups, query-parallel over nthreads host threads. dist_out != nullptr: row k of it (ld >= n
-// elements apart) gets group k's distances, -1 for unreached vertices; columns [n, ld) stay.
-// parent_out != nullptr: row k of it (same stride) gets group k's parents (cpu_parent_row).
+// One group's level profile (RunOutputs: reach, ecc, hist) from its distance array (as
+// cpu_msbfs_F leaves it), into row k of out's arrays
+void cpu_profile_row(const int32_t* dist, int64_t n, int64_t k, const RunOutputs& out);
+// All groups, query-parallel over nthreads host threads; edges: the halved degree sums (see
+// cpu_msbfs_F). out (host memory, not checked here: RunOutputs::validate is the callers'): each
+// array that is there is written, row k from group k's distance array; the parents
+// (cpu_parent_row) also without a distance matrix.
 void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
-                   std::vector<int64_t>* edges, int nthreads, int32_t* dist_out = nullptr,
-                   int64_t ld = 0, int32_t* parent_out = nullptr,
-                   const CpuProfile* profile = nullptr);
+                   std::vector<int64_t>* edges, int nthreads, const RunOutputs& out = {});
 
 // Reference tie-break (main.cu:381-397): first valid F, then strict '<'; returns -1 if K==0.
 int64_t argmin_first(const std::vector<int64_t>& F);

@@ -21,10 +21,10 @@ struct msbfs_solver_s {
   std::unique_ptr<msbfs::Solver> impl;
   int nthreads = 0;
   std::vector<msbfs::LevelRec> recs;  // per-level records of the last run / phase
-  // host-output distance runs: one solver pass of rows on the device, a pinned chunk on the host
-  msbfs::DevBuf dist_stage;
+  // host-output distance / parents runs: one solver pass of rows per matrix on the device, a
+  // pinned chunk on the host
+  msbfs::DevBuf stage[2];
   std::unique_ptr<msbfs::PinnedBuf> dist_pinned;
-  msbfs::DevBuf parent_stage;  // (host-output parents runs: the second matrix's rows)
 };
 
 namespace {
@@ -58,6 +58,33 @@ hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 // solver stages one pass), and the pinned chunk the rows come down through
 constexpr int64_t kDistStageBudget = int64_t{256} << 20;
 constexpr int64_t kDistPinnedBytes = int64_t{16} << 20;
+
+void check_queries(const std::string& who, int64_t K, const int64_t* qoff, const int32_t* qids,
+                   const int64_t* F) {
+  if (K < 0 || (K > 0 && (!qoff || !F))) msbfs::fail(who + ": bad query set");
+  if (K > 0 && qoff[K] > qoff[0] && !qids) msbfs::fail(who + ": bad query set");
+}
+
+// The msbfs_cpu_run* functions: the graph and the queries from their arrays, through the oracle
+// (edges: its halved counts)
+void cpu_run(const char* who, int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
+             const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges, int nthreads,
+             const msbfs::RunOutputs& out) {
+  out.validate(n, who, K);
+  if (K <= 0) return;
+  msbfs::HostCsr g;
+  g.n = n;
+  g.rowptr.assign(rowptr, rowptr + n + 1);
+  g.col.assign(col, col + rowptr[n]);
+  g.m = rowptr[n] / 2;
+  msbfs::QuerySet q;
+  q.off.assign(qoff, qoff + K + 1);
+  q.ids.assign(qids, qids + qoff[K]);
+  std::vector<int64_t> f, e;
+  msbfs::cpu_msbfs_all(g, q, f, edges ? &e : nullptr, nthreads, out);
+  std::memcpy(F, f.data(), K * sizeof(int64_t));
+  if (edges) std::memcpy(edges, e.data(), K * sizeof(int64_t));
+}
 }  // namespace
 
 // run fn on the solver's device stream with event timing and fill st
@@ -216,20 +243,7 @@ int msbfs_gen_queries(int64_t n, int64_t K, int64_t size, uint64_t seed, int64_t
 int msbfs_cpu_run(int64_t n, const int64_t* rowptr, const int32_t* col, int64_t K,
                   const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges,
                   int nthreads) {
-  return guard([&] {
-    msbfs::HostCsr g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + rowptr[n]);
-    g.m = rowptr[n] / 2;
-    msbfs::QuerySet q;
-    q.off.assign(qoff, qoff + K + 1);
-    q.ids.assign(qids, qids + qoff[K]);
-    std::vector<int64_t> f, e;
-    msbfs::cpu_msbfs_all(g, q, f, edges ? &e : nullptr, nthreads);
-    std::memcpy(F, f.data(), K * sizeof(int64_t));
-    if (edges) std::memcpy(edges, e.data(), K * sizeof(int64_t));
-  });
+  return guard([&] { cpu_run("cpu_run", n, rowptr, col, K, qoff, qids, F, edges, nthreads, {}); });
 }
 
 int msbfs_graph_from_host_csr(int device, int64_t n, const int64_t* rowptr, const int32_t* col,
@@ -438,7 +452,7 @@ int msbfs_solver_run(msbfs_solver s, int64_t K, const int64_t* qoff, const int32
                      int64_t* F, int64_t* edges2, msbfs_stats* st, void* stream) {
   return guard([&] {
     timed(s, stream, st, "solver run", [&](msbfs::RunStats* rs, hipStream_t hs) {
-      s->impl->run(K, qoff, qids, F, edges2, rs, hs);
+      s->impl->run(K, qoff, qids, F, edges2, {}, rs, hs);
     });
   });
 }
@@ -457,23 +471,53 @@ struct pinned_copy {
     MSBFS_HIP_CHECK(hipStreamSynchronize(hs));
   }
 };
-void check_dist_args(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
-                     const int64_t* F, const void* dist, int64_t ld) {
+// The device runs with outputs: the argument checks, then the run (of K > 0 groups), timed.
+// staged: out's matrices are host memory. A slab of `rows` groups per matrix is staged on the
+// device (the per-group solvers' byte budget is shared out among the matrices) and comes down
+// through one pinned chunk, the distances first.
+void run_out(msbfs_solver s, const char* what, int64_t K, const int64_t* qoff,
+             const int32_t* qids, int64_t* F, const msbfs::RunOutputs& out, msbfs_stats* st,
+             void* stream, bool staged = false) {
+  const char* who = out.asked == msbfs::RunOutputs::kProfile ? "run_profile" : "run_dist";
   if (!s || !s->impl) msbfs::fail("null solver");
-  if (K < 0 || (K > 0 && (!qoff || !F))) msbfs::fail("run_dist: bad query set");
-  if (K > 0 && qoff[K] > qoff[0] && !qids) msbfs::fail("run_dist: bad query set");
-  if (K > 0 && !dist) msbfs::fail("run_dist: no distance output");
-  if (ld < s->graph->g.n) msbfs::fail("run_dist: ld must be at least n");
+  check_queries(who, K, qoff, qids, F);
+  const int64_t n = s->graph->g.n;
+  out.validate(n, who, K);
+  timed(s, stream, st, what, [&](msbfs::RunStats* rs, hipStream_t hs) {
+    if (K <= 0) return;
+    if (!staged) return s->impl->run(K, qoff, qids, F, nullptr, out, rs, hs);
+    int32_t* const host[2] = {out.dist, out.parent};
+    const int count = out.parent ? 2 : 1;
+    const int64_t rows =
+        msbfs::dist_stage_rows(s->impl->pass_groups(), K, n, kDistStageBudget / count);
+    // (an allocation that fails throws; the guard turns it into an error return)
+    msbfs::RunOutputs dev = out;
+    dev.ld = n;
+    for (int m = 0; m < count; ++m) {
+      s->stage[m].ensure((size_t)rows * std::max<int64_t>(n, 1) * sizeof(int32_t));
+      (m ? dev.parent : dev.dist) = s->stage[m].as<int32_t>();
+    }
+    const int64_t chunk =
+        std::min<int64_t>(kDistPinnedBytes / (int64_t)sizeof(int32_t), std::max<int64_t>(rows * n, 1));
+    if (!s->dist_pinned || s->dist_pinned->bytes < (size_t)chunk * sizeof(int32_t))
+      s->dist_pinned = std::make_unique<msbfs::PinnedBuf>((size_t)chunk * sizeof(int32_t));
+    int32_t* pin = s->dist_pinned->as<int32_t>();
+    for (int64_t k0 = 0; k0 < K; k0 += rows) {
+      const int64_t nb = std::min(rows, K - k0);
+      s->impl->run(nb, qoff + k0, qids, F + k0, nullptr, dev, rs, hs);
+      for (int m = 0; m < count; ++m)
+        msbfs::dist_stage_download(pinned_copy(s->stage[m].as<int32_t>(), pin, hs), nb, n, chunk,
+                                   out.ld, pin, host[m] + k0 * out.ld);
+    }
+  });
 }
 }  // namespace
 
 int msbfs_solver_run_dist(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
                           int64_t* F, void* dist_dev, int64_t ld, msbfs_stats* st, void* stream) {
   return guard([&] {
-    check_dist_args(s, K, qoff, qids, F, dist_dev, ld);
-    timed(s, stream, st, "solver run_dist", [&](msbfs::RunStats* rs, hipStream_t hs) {
-      if (K > 0) s->impl->run_dist(K, qoff, qids, F, (int32_t*)dist_dev, ld, rs, hs);
-    });
+    run_out(s, "solver run_dist", K, qoff, qids, F,
+            msbfs::RunOutputs::distances((int32_t*)dist_dev, ld), st, stream);
   });
 }
 
@@ -481,26 +525,8 @@ int msbfs_solver_run_dist_host(msbfs_solver s, int64_t K, const int64_t* qoff,
                                const int32_t* qids, int64_t* F, int32_t* dist_host, int64_t ld,
                                msbfs_stats* st, void* stream) {
   return guard([&] {
-    check_dist_args(s, K, qoff, qids, F, dist_host, ld);
-    const int64_t n = s->graph->g.n;
-    timed(s, stream, st, "solver run_dist_host", [&](msbfs::RunStats* rs, hipStream_t hs) {
-      if (K <= 0) return;
-      const int64_t rows = msbfs::dist_stage_rows(s->impl->pass_groups(), K, n, kDistStageBudget);
-      // (an allocation that fails throws; the guard turns it into an error return)
-      s->dist_stage.ensure((size_t)rows * std::max<int64_t>(n, 1) * sizeof(int32_t));
-      const int64_t chunk =
-          std::min<int64_t>(kDistPinnedBytes / (int64_t)sizeof(int32_t), std::max<int64_t>(rows * n, 1));
-      if (!s->dist_pinned || s->dist_pinned->bytes < (size_t)chunk * sizeof(int32_t))
-        s->dist_pinned = std::make_unique<msbfs::PinnedBuf>((size_t)chunk * sizeof(int32_t));
-      int32_t* dev = s->dist_stage.as<int32_t>();
-      int32_t* pin = s->dist_pinned->as<int32_t>();
-      for (int64_t k0 = 0; k0 < K; k0 += rows) {
-        const int64_t nb = std::min(rows, K - k0);
-        s->impl->run_dist(nb, qoff + k0, qids, F + k0, dev, n, rs, hs);
-        msbfs::dist_stage_download(pinned_copy(dev, pin, hs), nb, n, chunk, ld, pin,
-                                   dist_host + k0 * ld);
-      }
-    });
+    run_out(s, "solver run_dist_host", K, qoff, qids, F,
+            msbfs::RunOutputs::distances(dist_host, ld), st, stream, true);
   });
 }
 
@@ -509,19 +535,8 @@ int msbfs_cpu_run_dist(int64_t n, const int64_t* rowptr, const int32_t* col, int
                        int64_t ld, int nthreads) {
   return guard([&] {
     if (n < 0 || K < 0 || (K > 0 && (!qoff || !F || !dist))) msbfs::fail("cpu_run_dist: bad arguments");
-    if (ld < n) msbfs::fail("cpu_run_dist: ld must be at least n");
-    if (K == 0) return;
-    msbfs::HostCsr g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + rowptr[n]);
-    g.m = rowptr[n] / 2;
-    msbfs::QuerySet q;
-    q.off.assign(qoff, qoff + K + 1);
-    q.ids.assign(qids, qids + qoff[K]);
-    std::vector<int64_t> f;
-    msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, dist, ld);
-    std::memcpy(F, f.data(), K * sizeof(int64_t));
+    cpu_run("cpu_run_dist", n, rowptr, col, K, qoff, qids, F, nullptr, nthreads,
+            msbfs::RunOutputs::distances(dist, ld));
   });
 }
 
@@ -531,12 +546,8 @@ int msbfs_solver_run_parents(msbfs_solver s, int64_t K, const int64_t* qoff, con
                              int64_t* F, void* dist_dev, void* parent_dev, int64_t ld,
                              msbfs_stats* st, void* stream) {
   return guard([&] {
-    check_dist_args(s, K, qoff, qids, F, dist_dev, ld);
-    if (K > 0 && !parent_dev) msbfs::fail("run_parents: no parent output");
-    timed(s, stream, st, "solver run_parents", [&](msbfs::RunStats* rs, hipStream_t hs) {
-      if (K > 0)
-        s->impl->run_parents(K, qoff, qids, F, (int32_t*)dist_dev, (int32_t*)parent_dev, ld, rs, hs);
-    });
+    run_out(s, "solver run_parents", K, qoff, qids, F,
+            msbfs::RunOutputs::parents((int32_t*)dist_dev, (int32_t*)parent_dev, ld), st, stream);
   });
 }
 
@@ -545,32 +556,8 @@ int msbfs_solver_run_parents_host(msbfs_solver s, int64_t K, const int64_t* qoff
                                   int32_t* parent_host, int64_t ld, msbfs_stats* st,
                                   void* stream) {
   return guard([&] {
-    check_dist_args(s, K, qoff, qids, F, dist_host, ld);
-    if (K > 0 && !parent_host) msbfs::fail("run_parents: no parent output");
-    const int64_t n = s->graph->g.n;
-    timed(s, stream, st, "solver run_parents_host", [&](msbfs::RunStats* rs, hipStream_t hs) {
-      if (K <= 0) return;
-      // (two staged matrices: each gets half of the per-group solvers' byte budget)
-      const int64_t rows =
-          msbfs::dist_stage_rows(s->impl->pass_groups(), K, n, kDistStageBudget / 2);
-      const size_t stage_bytes = (size_t)rows * std::max<int64_t>(n, 1) * sizeof(int32_t);
-      s->dist_stage.ensure(stage_bytes);
-      s->parent_stage.ensure(stage_bytes);
-      const int64_t chunk =
-          std::min<int64_t>(kDistPinnedBytes / (int64_t)sizeof(int32_t), std::max<int64_t>(rows * n, 1));
-      if (!s->dist_pinned || s->dist_pinned->bytes < (size_t)chunk * sizeof(int32_t))
-        s->dist_pinned = std::make_unique<msbfs::PinnedBuf>((size_t)chunk * sizeof(int32_t));
-      int32_t* pin = s->dist_pinned->as<int32_t>();
-      int32_t* const dev[2] = {s->dist_stage.as<int32_t>(), s->parent_stage.as<int32_t>()};
-      int32_t* const host[2] = {dist_host, parent_host};
-      for (int64_t k0 = 0; k0 < K; k0 += rows) {
-        const int64_t nb = std::min(rows, K - k0);
-        s->impl->run_parents(nb, qoff + k0, qids, F + k0, dev[0], dev[1], n, rs, hs);
-        for (int m = 0; m < 2; ++m)
-          msbfs::dist_stage_download(pinned_copy(dev[m], pin, hs), nb, n, chunk, ld, pin,
-                                     host[m] + k0 * ld);
-      }
-    });
+    run_out(s, "solver run_parents_host", K, qoff, qids, F,
+            msbfs::RunOutputs::parents(dist_host, parent_host, ld), st, stream, true);
   });
 }
 
@@ -580,42 +567,17 @@ int msbfs_cpu_run_parents(int64_t n, const int64_t* rowptr, const int32_t* col, 
   return guard([&] {
     if (n < 0 || K < 0 || (K > 0 && (!qoff || !F || !dist || !parent)))
       msbfs::fail("cpu_run_parents: bad arguments");
-    if (ld < n) msbfs::fail("cpu_run_parents: ld must be at least n");
-    if (K == 0) return;
-    msbfs::HostCsr g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + rowptr[n]);
-    g.m = rowptr[n] / 2;
-    msbfs::QuerySet q;
-    q.off.assign(qoff, qoff + K + 1);
-    q.ids.assign(qids, qids + qoff[K]);
-    std::vector<int64_t> f;
-    msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, dist, ld, parent);
-    std::memcpy(F, f.data(), K * sizeof(int64_t));
+    cpu_run("cpu_run_parents", n, rowptr, col, K, qoff, qids, F, nullptr, nthreads,
+            msbfs::RunOutputs::parents(dist, parent, ld));
   });
 }
-
-namespace {
-void check_profile_args(const char* who, int64_t K, const int64_t* qoff, const int32_t* qids,
-                        const int64_t* F, const int64_t* hist, int64_t nbins, int64_t ld) {
-  const std::string w(who);
-  if (K < 0 || (K > 0 && (!qoff || !F))) msbfs::fail(w + ": bad query set");
-  if (K > 0 && qoff[K] > qoff[0] && !qids) msbfs::fail(w + ": bad query set");
-  if (nbins < 1) msbfs::fail(w + ": nbins must be at least 1");
-  if (hist && ld < nbins) msbfs::fail(w + ": ld must be at least nbins");
-}
-}  // namespace
 
 int msbfs_solver_run_profile(msbfs_solver s, int64_t K, const int64_t* qoff, const int32_t* qids,
                              int64_t* F, int64_t* reach, int32_t* ecc, int64_t* hist,
                              int64_t nbins, int64_t ld, msbfs_stats* st, void* stream) {
   return guard([&] {
-    if (!s || !s->impl) msbfs::fail("null solver");
-    check_profile_args("run_profile", K, qoff, qids, F, hist, nbins, ld);
-    timed(s, stream, st, "solver run_profile", [&](msbfs::RunStats* rs, hipStream_t hs) {
-      if (K > 0) s->impl->run_profile(K, qoff, qids, F, reach, ecc, hist, nbins, ld, rs, hs);
-    });
+    run_out(s, "solver run_profile", K, qoff, qids, F,
+            msbfs::RunOutputs::profile(reach, ecc, hist, nbins, ld), st, stream);
   });
 }
 
@@ -624,21 +586,9 @@ int msbfs_cpu_run_profile(int64_t n, const int64_t* rowptr, const int32_t* col, 
                           int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, int nthreads) {
   return guard([&] {
     if (n < 0) msbfs::fail("cpu_run_profile: bad arguments");
-    check_profile_args("cpu_run_profile", K, qoff, qids, F, hist, nbins, ld);
-    if (K == 0) return;
-    msbfs::HostCsr g;
-    g.n = n;
-    g.rowptr.assign(rowptr, rowptr + n + 1);
-    g.col.assign(col, col + rowptr[n]);
-    g.m = rowptr[n] / 2;
-    msbfs::QuerySet q;
-    q.off.assign(qoff, qoff + K + 1);
-    q.ids.assign(qids, qids + qoff[K]);
-    std::vector<int64_t> f;
-    msbfs::CpuProfile p;
-    p.reach = reach, p.ecc = ecc, p.hist = hist, p.nbins = nbins, p.ld = ld;
-    msbfs::cpu_msbfs_all(g, q, f, nullptr, nthreads, nullptr, 0, nullptr, &p);
-    std::memcpy(F, f.data(), K * sizeof(int64_t));
+    check_queries("cpu_run_profile", K, qoff, qids, F);
+    cpu_run("cpu_run_profile", n, rowptr, col, K, qoff, qids, F, nullptr, nthreads,
+            msbfs::RunOutputs::profile(reach, ecc, hist, nbins, ld));
   });
 }
 

@@ -60,8 +60,8 @@ void cpu_parent_row(const HostCsr& g, const int32_t* dist, int32_t* parent) {
   }
 }
 
-void cpu_profile_row(const int32_t* dist, int64_t n, int64_t k, const CpuProfile& p) {
-  int64_t* h = p.hist ? p.hist + k * p.ld : nullptr;
+void cpu_profile_row(const int32_t* dist, int64_t n, int64_t k, const RunOutputs& p) {
+  int64_t* h = p.hist ? p.hist + k * p.hist_ld : nullptr;
   if (h) std::fill(h, h + p.nbins, int64_t{0});
   int64_t reach = 0;
   int32_t mx = -1;
@@ -77,8 +77,7 @@ void cpu_profile_row(const int32_t* dist, int64_t n, int64_t k, const CpuProfile
 }
 
 void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
-                   std::vector<int64_t>* edges, int nthreads, int32_t* dist_out, int64_t ld,
-                   int32_t* parent_out, const CpuProfile* profile) {
+                   std::vector<int64_t>* edges, int nthreads, const RunOutputs& out) {
   const int64_t K = q.K();
   F.assign(K, 0);
   if (edges) edges->assign(K, 0);
@@ -95,9 +94,9 @@ void cpu_msbfs_all(const HostCsr& g, const QuerySet& q, std::vector<int64_t>& F,
       F[k] = cpu_msbfs_F(g, q.ids.data() + q.off[k], q.off[k + 1] - q.off[k], dist, queue, &e);
       if (edges) (*edges)[k] = e;
       // (the worker's distance array already is the row: -1 unreached, 0 the valid sources)
-      if (dist_out) std::copy(dist.begin(), dist.begin() + g.n, dist_out + k * ld);
-      if (parent_out) cpu_parent_row(g, dist.data(), parent_out + k * ld);
-      if (profile) cpu_profile_row(dist.data(), g.n, k, *profile);
+      if (out.dist) std::copy(dist.begin(), dist.begin() + g.n, out.dist + k * out.ld);
+      if (out.parent) cpu_parent_row(g, dist.data(), out.parent + k * out.ld);
+      if (out.asked == RunOutputs::kProfile) cpu_profile_row(dist.data(), g.n, k, out);
     }
   };
   if (nthreads == 1) {

@@ -490,7 +490,7 @@ __device__ __forceinline__ bool bu_gate_open(const BuGate& g) {
   return !g.c || bu_gate_eval(*g.c, g.beta, g.alpha, g.first);
 }
 
-// The per-group level counts of a profile run (BitparSolver::run_profile), kept where they already
+// The per-group level counts of a profile run (RunOutputs::kProfile), kept where they already
 // pass through on their way into F: hist[min(level, last) * 64 * W + group] += the level's count
 // (row `last` is the tail), unsigned and allowed to wrap until the batch ends (the leaf fold's
 // source corrections, k_leaf_sources). Those corrections touch levels 0-2 only and can take a

@@ -1,4 +1,4 @@
-// Bit-parallel MS-BFS: per-vertex distance output. A distance run (BitparSolver::run_dist) rides
+// Bit-parallel MS-BFS: per-vertex distance output. A distance run (RunOutputs::dist) rides
 // the edge-counting instantiation, the one mode in which every level leaves a materialised new
 // frontier list and an exact new-bit row per frontier vertex; right after each k_count_frontier
 // a k_record_levels launch stores the level number for every new (vertex, group) bit into the
@@ -20,7 +20,7 @@ struct Record {
   int64_t k0 = 0, nb = 0;          // the current batch's groups [k0, k0 + nb)
   const int32_t* new2old = nullptr;  // internal id -> user id (nullptr: the graph keeps its ids)
   int32_t* slot = nullptr;           // n marks of the dense walk (relabelled graphs), all zero
-  // a parents run (BitparSolver::run_parents): the BFS parent matrix, laid out like out, the
+  // a parents run (RunOutputs::parent): the BFS parent matrix, laid out like out, the
   // run's own seen rows and the wide search's queue (below); all nullptr in a plain distance run
   int32_t* parent = nullptr;
   uint64_t* seen = nullptr;
@@ -113,7 +113,7 @@ static __global__ __launch_bounds__(kBlock) void k_record_mark(const int32_t* fl
 // the dense walk pays from this share of the vertices on (an n-entry pass per level otherwise)
 constexpr int64_t kRecordDenseDiv = 16;
 
-// ---- BFS parents (BitparSolver::run_parents) ----------------------------------------------------
+// ---- BFS parents (RunOutputs::parent) -----------------------------------------------------------
 // parent[group * ld + user id of v] = user id of the FIRST neighbour u, in the order of v's row
 // in the device graph, that group reached one level before v. A parents run is a distance run
 // that also owns seen[n * W]: the (vertex, group) bits recorded through the previous level, by

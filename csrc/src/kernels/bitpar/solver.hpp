@@ -33,8 +33,9 @@
 //   bitpar/bits.hpp                      pure bit helpers (HIP-free, pinned by the host self-test)
 //   bitpar/common.hpp  init.hpp  push.hpp  hybrid.hpp  tiles.hpp      kernels by family; the pull
 //   bitpar/pull.hpp  pull_full.hpp  pull_lists.hpp  pull_tail.hpp     levels': pulls, lists, tail push
-//   bitpar/record.hpp                    the distance / parent output of run_dist, run_parents (per level)
-//   bitpar_solver.hip  construction, batches, the level loop (direction choice, reductions)
+//   bitpar/record.hpp                    the distance / parent output (RunOutputs::dist, parent), per level
+//   bitpar_solver.hip  construction, run() (one batch loop, the per-kind setup off
+//                      RunOutputs::kind), the level loop (direction choice, reductions)
 //   bitpar_push.hip    top-down levels and the device-driven level batches
 //   bitpar_pull.hip    bottom-up levels (prefix pull + tail push, narrow / lean / chunk pulls),
 //                      each carried out from a plan: bitpar/pull_plan.hpp (plain host code)
@@ -83,20 +84,12 @@ class BitparSolver final : public Solver {
  public:
   BitparSolver(const DeviceGraph& g, int max_groups);
 
+  // One batch loop for every kind of out. Distances (and parents, the first-in-row BFS parent:
+  // bitpar/record.hpp) force the edge-counting instantiation; a profile (reach, eccentricity,
+  // vertices per level) runs the same kernels and decisions as a plain run, the counts kept where
+  // they pass on their way into F.
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
-           RunStats* st, hipStream_t stream) override;
-  // run() plus dist_dev[k * ld + v] (bitpar/record.hpp); forces the edge-counting instantiation
-  void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
-                int64_t ld, RunStats* st, hipStream_t stream) override;
-  // run_dist() plus parent_dev[k * ld + v], the first-in-row BFS parent (bitpar/record.hpp)
-  void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                   int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
-                   hipStream_t stream) override;
-  // run() plus each group's level profile (reach, eccentricity, vertices per level): the same
-  // kernels and decisions as run(); the counts are kept where they pass on their way into F
-  void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
-                   int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, RunStats* st,
-                   hipStream_t stream) override;
+           const RunOutputs& out, RunStats* st, hipStream_t stream) override;
   void tune(const std::string& spec) override { tun_.parse(spec); }
   int64_t pass_groups() const override { return 64 * (int64_t)std::min(maxW_, opt.max_words); }
   // graph-derived tables and worst-case scratch, built before any timed run (bitpar_pull.hip)
@@ -195,8 +188,8 @@ class BitparSolver final : public Solver {
   template <int W, bool COUNT>
   void batch_impl(int64_t k0, int64_t nb, const int64_t* qoff, const int32_t* qids, int64_t* F,
                   int64_t* edges2, RunStats* st, hipStream_t s);
-  void run_batch(int w, int64_t k0, int64_t nb, const int64_t* qoff, const int32_t* qids,
-                 int64_t* F, int64_t* edges2, RunStats* st, hipStream_t s);
+  void run_batch(int w, bool count, int64_t k0, int64_t nb, const int64_t* qoff,
+                 const int32_t* qids, int64_t* F, int64_t* edges2, RunStats* st, hipStream_t s);
   // ---- bitpar_push.hip: one top-down level (returns the counter-slab rows it wrote)
   template <int W, bool COUNT>
   int level_td(Loop& S, hipStream_t s);
@@ -499,14 +492,11 @@ class BitparSolver final : public Solver {
   }
   DevBuf bctr_;  // (kBatch+1) Ctr slots, then (kBatch+1) x 16 alive words
   // ---- distance output (bitpar/record.hpp)
-  Record rec_;     // set by run_dist for its duration; rec_.out == nullptr otherwise
+  Record rec_;     // set by a distance run for its duration; rec_.out == nullptr otherwise
   InverseMap n2o_;  // inverse of g_.old2new, built on first use, cached per map
   DevBuf rslot_;   // the dense walk's marks (record.hpp), n int32, zero between levels
   DevBuf seen_;    // a parents run's seen rows (record.hpp), n * W words, zeroed per batch
   DevBuf wq_;      // its wide queue: a counter (first 16 bytes), then n vertex ids
-  void run_dist_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                     int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
-                     hipStream_t stream);
   // the level-0 zeros of a batch's source pairs / one level's new bits off the new frontier list
   // fl_[fc ^ 1] (length from ctr; new bits = a, or a & ~b with DIFF), right after the level's
   // k_count_frontier. Both launch nothing unless a distance run is under way; in a parents run
@@ -543,16 +533,9 @@ class BitparSolver final : public Solver {
     MSBFS_HIP_CHECK(hipGetLastError());
   }
   std::unique_ptr<PinnedBuf> hbctr_;
-  // ---- level profiles (run_profile; Prof in bitpar/common.hpp)
-  // What a profile run asked for (host memory, whole run; a batch writes its groups' part)
-  struct ProfOut {
-    int64_t* reach = nullptr;
-    int32_t* ecc = nullptr;
-    int64_t* hist = nullptr;
-    int64_t nbins = 0, ld = 0;  // (nbins = 0: no histogram asked for)
-    bool on = false;
-  };
-  ProfOut pout_;
+  // ---- level profiles (Prof in bitpar/common.hpp)
+  // What a profile run asked for (whole run; a batch writes its groups' part), plain otherwise
+  RunOutputs pout_;
   Prof prof_;  // the current batch's device counts; prof_.hist == nullptr outside a profile run
   // far[64 * 16], then the histogram rows (rows x 64 * W of the batch); the batch's results
   // (reach, ecc, the capped histogram group-major) on the device and in pinned memory

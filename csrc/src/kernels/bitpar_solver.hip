@@ -65,11 +65,66 @@ BitparSolver::BitparSolver(const DeviceGraph& g, int max_groups)
 }
 
 void BitparSolver::run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                       int64_t* edges2, RunStats* st, hipStream_t stream) {
-  const int64_t builds0 = plen_builds_;
+                       int64_t* edges2, const RunOutputs& out, RunStats* st, hipStream_t stream) {
+  const RunOutputs::Kind kind = out.kind(edges2 != nullptr);
+  out.validate(g_.n);
+  if (kind == RunOutputs::kProfile && out.nbins > INT32_MAX / 2) fail("run_profile: too many bins");
+  const bool matrices = kind == RunOutputs::kDist || kind == RunOutputs::kParents;
+  const bool parents = kind == RunOutputs::kParents;
+  // (cleared however the run ends: a later run must launch and count nothing of this one)
+  struct Scope {
+    BitparSolver& b;
+    ~Scope() {
+      b.rec_ = Record{};
+      b.pout_ = RunOutputs{};
+      b.prof_ = Prof{};
+    }
+  } scope{*this};
+  const int64_t n = g_.n;
   const int mw = std::min(maxW_, opt.max_words);
+  const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+  if (kind == RunOutputs::kProfile) pout_ = out;
+  if (matrices) {
+    rec_.out = out.dist;
+    rec_.ld = out.ld;
+    rec_.new2old = n2o_.get(g_, stream);
+    if (rec_.new2old && n > 0) {
+      // (zeroed per run: a run that failed half way may have left marks)
+      rslot_.ensure((size_t)n * sizeof(int32_t));
+      MSBFS_HIP_CHECK(hipMemsetAsync(rslot_.p, 0, (size_t)n * sizeof(int32_t), stream));
+      rec_.slot = rslot_.as<int32_t>();
+    }
+  }
+  if (parents) {
+    seen_.ensure(n1 * mw * sizeof(uint64_t));
+    rec_.parent = out.parent;
+    rec_.seen = seen_.as<uint64_t>();
+    wq_.ensure(16 + n1 * sizeof(int32_t));
+    // (zeroed per run: a run that failed half way may have left a count)
+    MSBFS_HIP_CHECK(hipMemsetAsync(wq_.p, 0, 16, stream));
+    rec_.wcnt = wq_.as<uint32_t>();
+    rec_.wq = wq_.as<int32_t>() + 4;
+  }
+  // the edge-counting instantiation: asked for, or a distance run (bitpar/record.hpp)
+  const bool count = edges2 != nullptr || opt.count_edges || matrices;
+  const int64_t builds0 = plen_builds_;
   for (Batch b = batch_at(K, 0, mw); b.k0 < K; b = batch_at(K, b.k0 + b.nb, mw)) {
-    run_batch(b.w, b.k0, b.nb, qoff, qids, F + b.k0, edges2 ? edges2 + b.k0 : nullptr, st, stream);
+    rec_.k0 = b.k0;
+    rec_.nb = b.nb;
+    // the -1 fill of the pass's rows, columns [0, n) only
+    for (int32_t* m : {out.dist, out.parent}) {
+      if (!m || n <= 0) continue;
+      int32_t* rows = m + b.k0 * out.ld;
+      if (out.ld == n)
+        MSBFS_HIP_CHECK(hipMemsetAsync(rows, 0xFF, (size_t)b.nb * n * sizeof(int32_t), stream));
+      else
+        MSBFS_HIP_CHECK(hipMemset2DAsync(rows, (size_t)out.ld * sizeof(int32_t), 0xFF,
+                                         (size_t)n * sizeof(int32_t), (size_t)b.nb, stream));
+    }
+    // (the batch's seen rows: b.w words per vertex)
+    if (parents) MSBFS_HIP_CHECK(hipMemsetAsync(seen_.p, 0, n1 * b.w * sizeof(uint64_t), stream));
+    run_batch(b.w, count, b.k0, b.nb, qoff, qids, F + b.k0, edges2 ? edges2 + b.k0 : nullptr, st,
+              stream);
     if (st) st->batches++;
   }
   if (st) st->builds += plen_builds_ - builds0;
@@ -116,9 +171,9 @@ void BitparSolver::prof_reserve(int w, int64_t nbins) {
 template <int W>
 void BitparSolver::prof_begin(hipStream_t s) {
   prof_ = Prof{};
-  if (!pout_.on) return;
-  prof_reserve(W, pout_.nbins);
-  const int64_t rows = prof_rows(pout_.nbins);
+  if (pout_.asked != RunOutputs::kProfile) return;
+  prof_reserve(W, pout_.bins());
+  const int64_t rows = prof_rows(pout_.bins());
   MSBFS_HIP_CHECK(hipMemsetAsync(
       prof_buf_.p, 0, 64 * 16 * sizeof(uint32_t) + (size_t)rows * 64 * W * sizeof(uint64_t), s));
   prof_.far = prof_buf_.as<uint32_t>();
@@ -130,42 +185,25 @@ template <int W>
 void BitparSolver::prof_finish(int64_t nb, hipStream_t s) {
   if (!prof_.hist) return;
   k_profile_finish<<<grid_for(nb, kBlock), kBlock, 0, s>>>(
-      prof_, (int)prof_.last + 1, 64 * W, nb, pout_.nbins, prof_res_.as<long long>());
+      prof_, (int)prof_.last + 1, 64 * W, nb, pout_.bins(), prof_res_.as<long long>());
   MSBFS_HIP_CHECK(hipGetLastError());
   MSBFS_HIP_CHECK(hipMemcpyAsync(hprof_->p, prof_res_.p,
-                                 (size_t)(2 + pout_.nbins) * nb * sizeof(int64_t),
+                                 (size_t)(2 + pout_.bins()) * nb * sizeof(int64_t),
                                  hipMemcpyDeviceToHost, s));
 }
 
 void BitparSolver::prof_store(int64_t k0, int64_t nb) {
   if (!prof_.hist) return;
   const int64_t* r = hprof_->as<int64_t>();
+  const int64_t nbins = pout_.bins();
   for (int64_t k = 0; k < nb; ++k) {
     if (pout_.reach) pout_.reach[k0 + k] = r[k];
     if (pout_.ecc) pout_.ecc[k0 + k] = (int32_t)r[nb + k];
     if (pout_.hist)
-      std::copy(r + 2 * nb + k * pout_.nbins, r + 2 * nb + (k + 1) * pout_.nbins,
-                pout_.hist + (k0 + k) * pout_.ld);
+      std::copy(r + 2 * nb + k * nbins, r + 2 * nb + (k + 1) * nbins,
+                pout_.hist + (k0 + k) * pout_.hist_ld);
   }
   prof_ = Prof{};
-}
-
-void BitparSolver::run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                               int64_t* reach, int32_t* ecc, int64_t* hist, int64_t nbins,
-                               int64_t ld, RunStats* st, hipStream_t stream) {
-  if (nbins < 1) fail("run_profile: nbins must be at least 1");
-  if (hist && ld < nbins) fail("run_profile: ld must be at least nbins");
-  if (nbins > INT32_MAX / 2) fail("run_profile: too many bins");
-  // (cleared however the run ends: a later run() must count nothing of this)
-  struct Scope {
-    BitparSolver& b;
-    ~Scope() {
-      b.pout_ = ProfOut{};
-      b.prof_ = Prof{};
-    }
-  } scope{*this};
-  pout_ = ProfOut{reach, ecc, hist, hist ? nbins : 0, ld, true};
-  run(K, qoff, qids, F, nullptr, st, stream);
 }
 
 // ---- distance output (bitpar/record.hpp) --------------------------------------------------------
@@ -198,78 +236,9 @@ void BitparSolver::record_sources(const int32_t* pv, const int32_t* pk, int64_t 
   MSBFS_HIP_CHECK(hipGetLastError());
 }
 
-void BitparSolver::run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                            int32_t* dist_dev, int64_t ld, RunStats* st, hipStream_t stream) {
-  run_dist_impl(K, qoff, qids, F, dist_dev, nullptr, ld, st, stream);
-}
-
-void BitparSolver::run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                               int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
-                               hipStream_t stream) {
-  if (!parent_dev) fail("run_parents: no parent output");
-  run_dist_impl(K, qoff, qids, F, dist_dev, parent_dev, ld, st, stream);
-}
-
-// parent_dev != nullptr: a parents run
-void BitparSolver::run_dist_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                                 int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
-                                 hipStream_t stream) {
-  const int64_t n = g_.n;
-  if (!dist_dev) fail("run_dist: no distance output");
-  if (ld < n) fail("run_dist: ld must be at least n");
-  // (cleared however the run ends: a later run() must launch nothing of this)
-  struct Scope {
-    Record& r;
-    ~Scope() { r = Record{}; }
-  } scope{rec_};
-  rec_.out = dist_dev;
-  rec_.ld = ld;
-  rec_.new2old = n2o_.get(g_, stream);
-  if (rec_.new2old && n > 0) {
-    // (zeroed per run: a run that failed half way may have left marks)
-    rslot_.ensure((size_t)n * sizeof(int32_t));
-    MSBFS_HIP_CHECK(hipMemsetAsync(rslot_.p, 0, (size_t)n * sizeof(int32_t), stream));
-    rec_.slot = rslot_.as<int32_t>();
-  }
-  const int64_t builds0 = plen_builds_;
-  const int mw = std::min(maxW_, opt.max_words);
-  const size_t n1 = (size_t)std::max<int64_t>(n, 1);
-  if (parent_dev) {
-    seen_.ensure(n1 * mw * sizeof(uint64_t));
-    rec_.parent = parent_dev;
-    rec_.seen = seen_.as<uint64_t>();
-    wq_.ensure(16 + n1 * sizeof(int32_t));
-    // (zeroed per run: a run that failed half way may have left a count)
-    MSBFS_HIP_CHECK(hipMemsetAsync(wq_.p, 0, 16, stream));
-    rec_.wcnt = wq_.as<uint32_t>();
-    rec_.wq = wq_.as<int32_t>() + 4;
-  }
-  for (Batch b = batch_at(K, 0, mw); b.k0 < K; b = batch_at(K, b.k0 + b.nb, mw)) {
-    rec_.k0 = b.k0;
-    rec_.nb = b.nb;
-    // the -1 fill of the pass's rows, columns [0, n) only
-    for (int32_t* m : {dist_dev, parent_dev}) {
-      if (!m || n <= 0) continue;
-      int32_t* rows = m + b.k0 * ld;
-      if (ld == n)
-        MSBFS_HIP_CHECK(hipMemsetAsync(rows, 0xFF, (size_t)b.nb * n * sizeof(int32_t), stream));
-      else
-        MSBFS_HIP_CHECK(hipMemset2DAsync(rows, (size_t)ld * sizeof(int32_t), 0xFF,
-                                         (size_t)n * sizeof(int32_t), (size_t)b.nb, stream));
-    }
-    // (the batch's seen rows: b.w words per vertex)
-    if (parent_dev)
-      MSBFS_HIP_CHECK(hipMemsetAsync(seen_.p, 0, n1 * b.w * sizeof(uint64_t), stream));
-    run_batch(b.w, b.k0, b.nb, qoff, qids, F + b.k0, nullptr, st, stream);
-    if (st) st->batches++;
-  }
-  if (st) st->builds += plen_builds_ - builds0;
-}
-
-void BitparSolver::run_batch(int w, int64_t k0, int64_t nb, const int64_t* qoff,
+void BitparSolver::run_batch(int w, bool c, int64_t k0, int64_t nb, const int64_t* qoff,
                              const int32_t* qids, int64_t* F, int64_t* edges2, RunStats* st,
                              hipStream_t s) {
-  const bool c = edges2 != nullptr || opt.count_edges || rec_.out != nullptr;
 #define MSBFS_BP_CASE(WW)                                                   \
   case WW:                                                                  \
     if (c) batch_impl<WW, true>(k0, nb, qoff, qids, F, edges2, st, s);      \

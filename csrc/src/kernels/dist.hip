@@ -336,7 +336,7 @@ __global__ __launch_bounds__(kBlock) void k_reduce_fsum(const int32_t* dist, con
   }
 }
 
-// Distance output (Solver::run_dist): one group's row, out[v] = dist[old2new ? old2new[v] : v]
+// Distance output (RunOutputs::dist): one group's row, out[v] = dist[old2new ? old2new[v] : v]
 // for the user's ids v < n. Coalesced writes, a permutation gather on relabelled graphs; any
 // negative "unvisited" value comes out as -1.
 __global__ __launch_bounds__(kBlock) void k_gather_dist(const int32_t* dist,
@@ -355,12 +355,8 @@ static void gather_dist(const DeviceGraph& g, const int32_t* dist, int32_t* out_
   k_gather_dist<<<grid_for(g.n, kBlock, 4096), kBlock, 0, s>>>(dist, g.old2new, g.n, out_row);
   MSBFS_HIP_CHECK(hipGetLastError());
 }
-static void check_dist_out(const DeviceGraph& g, const int32_t* dist_dev, int64_t ld) {
-  if (!dist_dev) fail("run_dist: no distance output");
-  if (ld < g.n) fail("run_dist: ld must be at least n");
-}
 
-// Level profile (Solver::run_profile): one pass over a group's distance array next to the F sum.
+// Level profile (RunOutputs::reach, ecc, hist): one pass over a group's distance array next to the F sum.
 // out[0] += reached vertices, out[1] = max(distance + 1), out[2 + b] += vertices in bin b =
 // min(distance, nbins - 1) (nbins = 0: no bins). The first kProfLds bins are privatised in LDS
 // (one global atomic per bin with a count per block); a vertex of a later bin (more than
@@ -409,47 +405,8 @@ __global__ __launch_bounds__(kBlock) void k_profile_dist(const int32_t* dist, in
     if (b) atomicMax(&out[1], b);
   }
 }
-// What a profile run asked for (host memory, see Solver::run_profile) and its device scratch;
-// row(): group k's profile from its finished distance array
-struct ProfileOut {
-  int64_t* reach = nullptr;
-  int32_t* ecc = nullptr;
-  int64_t* hist = nullptr;
-  int64_t nbins = 0, ld = 0;
-  bool on = false;
-  DevBuf buf;
-  std::vector<unsigned long long> h;
-  void begin(int64_t* r, int32_t* e, int64_t* hi, int64_t nb, int64_t l) {
-    if (nb < 1) fail("run_profile: nbins must be at least 1");
-    if (hi && l < nb) fail("run_profile: ld must be at least nbins");
-    reach = r, ecc = e, hist = hi, nbins = hi ? nb : 0, ld = l;
-    buf.ensure((size_t)(2 + nbins) * sizeof(unsigned long long));
-    h.resize((size_t)(2 + nbins));
-    on = true;
-  }
-  void row(const int32_t* dist, int64_t n, int64_t k, hipStream_t s) {
-    if (!on) return;
-    const size_t bytes = (size_t)(2 + nbins) * sizeof(unsigned long long);
-    MSBFS_HIP_CHECK(hipMemsetAsync(buf.p, 0, bytes, s));
-    if (n > 0)
-      k_profile_dist<<<grid_for(n, kBlock, 1024), kBlock, 0, s>>>(dist, n, nbins,
-                                                                  buf.as<unsigned long long>());
-    MSBFS_HIP_CHECK(hipGetLastError());
-    MSBFS_HIP_CHECK(hipMemcpyAsync(h.data(), buf.p, bytes, hipMemcpyDeviceToHost, s));
-    MSBFS_HIP_CHECK(hipStreamSynchronize(s));
-    if (reach) reach[k] = (int64_t)h[0];
-    if (ecc) ecc[k] = (int32_t)((int64_t)h[1] - 1);
-    if (hist)
-      for (int64_t b = 0; b < nbins; ++b) hist[k * ld + b] = (int64_t)h[2 + b];
-  }
-};
-// (cleared however the run ends)
-struct ProfileScope {
-  ProfileOut& p;
-  ~ProfileScope() { p.on = false; }
-};
 
-// Parent output (Solver::run_parents): one group's row from the solver's own distance array,
+// Parent output (RunOutputs::parent): one group's row from the solver's own distance array,
 // over the internal ids i: out[user id of i] = -1 where unreached, the user's id itself for a
 // source, else the user's id of the first entry u of i's row with dist[u] == dist[i] - 1. Every
 // column below n is written. Rows from kParentsWideDegree entries on are scanned by the whole
@@ -524,10 +481,59 @@ static void load_code_dist(hipStream_t s) {
   MSBFS_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-class DistSolver final : public Solver {
+// What both per-group solvers share: the checks and scratch of a run, and the outputs of one
+// group from its finished distance array.
+class GroupSolver : public Solver {
  public:
   void prepare(hipStream_t s) override { load_code_dist(s); }
-  explicit DistSolver(const DeviceGraph& g) : g_(g) {
+
+ protected:
+  explicit GroupSolver(const DeviceGraph& g) : g_(g) {}
+  // before the first group: the argument checks, the source buffer and the outputs' scratch
+  void begin_run(int64_t K, const int64_t* qoff, const int64_t* edges2, const RunOutputs& out,
+                 hipStream_t s) {
+    out.kind(edges2 != nullptr);
+    out.validate(g_.n);
+    n2o_ = out.parent ? inv_.get(g_, s) : nullptr;
+    int64_t maxs = 1;
+    for (int64_t k = 0; k < K; ++k) maxs = std::max(maxs, qoff[k + 1] - qoff[k]);
+    src_.ensure((size_t)maxs * sizeof(int32_t));
+    if (out.asked == RunOutputs::kProfile) {
+      prof_.ensure((size_t)(2 + out.bins()) * sizeof(unsigned long long));
+      hprof_.resize((size_t)(2 + out.bins()));
+    }
+  }
+  // group k's rows of out (a distance row is gathered before the next group's reset of dist)
+  void group_outputs(const int32_t* dist, int64_t k, const RunOutputs& out, hipStream_t s) {
+    if (out.dist) gather_dist(g_, dist, out.dist + k * out.ld, s);
+    if (out.parent) parent_row(g_, dist, n2o_, out.parent + k * out.ld, s);
+    if (out.asked != RunOutputs::kProfile) return;
+    const int64_t nbins = out.bins();
+    const size_t bytes = (size_t)(2 + nbins) * sizeof(unsigned long long);
+    MSBFS_HIP_CHECK(hipMemsetAsync(prof_.p, 0, bytes, s));
+    if (g_.n > 0)
+      k_profile_dist<<<grid_for(g_.n, kBlock, 1024), kBlock, 0, s>>>(
+          dist, g_.n, nbins, prof_.as<unsigned long long>());
+    MSBFS_HIP_CHECK(hipGetLastError());
+    MSBFS_HIP_CHECK(hipMemcpyAsync(hprof_.data(), prof_.p, bytes, hipMemcpyDeviceToHost, s));
+    MSBFS_HIP_CHECK(hipStreamSynchronize(s));
+    if (out.reach) out.reach[k] = (int64_t)hprof_[0];
+    if (out.ecc) out.ecc[k] = (int32_t)((int64_t)hprof_[1] - 1);
+    for (int64_t b = 0; b < nbins; ++b) out.hist[k * out.hist_ld + b] = (int64_t)hprof_[2 + b];
+  }
+  const DeviceGraph& g_;
+  DevBuf src_;  // a group's sources
+
+ private:
+  InverseMap inv_;
+  const int32_t* n2o_ = nullptr;  // the run's new2old map (parents runs of a relabelled graph)
+  DevBuf prof_;                   // one group's profile: reach, max distance + 1, the bins
+  std::vector<unsigned long long> hprof_;
+};
+
+class DistSolver final : public GroupSolver {
+ public:
+  explicit DistSolver(const DeviceGraph& g) : GroupSolver(g) {
     const int64_t n = std::max<int64_t>(g.n, 1);
     dist_.alloc((size_t)n * sizeof(int32_t));
     MSBFS_HIP_CHECK(hipMemset(dist_.p, 0xFF, dist_.bytes));
@@ -545,40 +551,11 @@ class DistSolver final : public Solver {
     hslots_ = std::make_unique<PinnedBuf>((size_t)(kMaxBatch + 1) * sizeof(LevelSlot));
   }
 
+  // (a group's rows of out are written before the next group's lazy reset scatters -1 over dist_)
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
-           RunStats* st, hipStream_t s) override {
-    run_impl(K, qoff, qids, F, edges2, nullptr, nullptr, 0, st, s);
-  }
-  void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
-                int64_t ld, RunStats* st, hipStream_t s) override {
-    check_dist_out(g_, dist_dev, ld);
-    run_impl(K, qoff, qids, F, nullptr, dist_dev, nullptr, ld, st, s);
-  }
-  void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                   int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
-                   hipStream_t s) override {
-    check_dist_out(g_, dist_dev, ld);
-    if (!parent_dev) fail("run_parents: no parent output");
-    run_impl(K, qoff, qids, F, nullptr, dist_dev, parent_dev, ld, st, s);
-  }
-  void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
-                   int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, RunStats* st,
-                   hipStream_t s) override {
-    ProfileScope scope{prof_};
-    prof_.begin(reach, ecc, hist, nbins, ld);
-    run_impl(K, qoff, qids, F, nullptr, nullptr, nullptr, 0, st, s);
-  }
-
- private:
-  // dout != nullptr: row k of it gets group k's distances (gathered before the next group's
-  // lazy reset scatters -1 over them); pout != nullptr: row k of it the parents, likewise
-  void run_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
-                int32_t* dout, int32_t* pout, int64_t ld, RunStats* st, hipStream_t s) {
-    const int32_t* n2o = pout ? inv_.get(g_, s) : nullptr;
+           const RunOutputs& out, RunStats* st, hipStream_t s) override {
+    begin_run(K, qoff, edges2, out, s);
     const int64_t n = g_.n;
-    int64_t maxs = 1;
-    for (int64_t k = 0; k < K; ++k) maxs = std::max(maxs, qoff[k + 1] - qoff[k]);
-    src_.ensure((size_t)maxs * sizeof(int32_t));
     // device-driven top-down batches where every frontier vertex has few edges (road-like)
     const bool dd = g_.max_degree <= 64 && opt.force_dir != 2;
     for (int64_t k = 0; k < K; ++k) {
@@ -708,34 +685,29 @@ class DistSolver final : public Solver {
         ++L;
         if (st) st->levels++;
       }
-      if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
-      if (pout) parent_row(g_, dist_.as<int32_t>(), n2o, pout + k * ld, s);
-      prof_.row(dist_.as<int32_t>(), n, k, s);
+      group_outputs(dist_.as<int32_t>(), k, out, s);
       visited_ = lo + nf;  // every visited vertex sits in ord[0, lo + nf)
       F[k] = Fk;
       if (edges2) edges2[k] = E2;
     }
   }
 
+ private:
   HostCtr read(hipStream_t s) {
     MSBFS_HIP_CHECK(hipMemcpyAsync(hctr_->p, ctr_.p, sizeof(Ctr), hipMemcpyDeviceToHost, s));
     MSBFS_HIP_CHECK(hipStreamSynchronize(s));
     const Ctr* c = hctr_->as<Ctr>();
     return HostCtr{c->fl2.v, c->ul2.v, c->ulw2.v, c->updated.v, c->ef2.v, c->eu2.v};
   }
-  const DeviceGraph& g_;
-  DevBuf dist_, ord_, ul_[2], ulw_[2], offs_, scan_tmp_, ctr_, src_, slots_;
+  DevBuf dist_, ord_, ul_[2], ulw_[2], offs_, scan_tmp_, ctr_, slots_;
   size_t scan_bytes_ = 0;
-  InverseMap inv_;
-  ProfileOut prof_;
   int64_t visited_ = 0;  // vertices the last group reached (ord[0, visited_) to reset)
   std::unique_ptr<PinnedBuf> hctr_, hslots_;
 };
 
-class SweepSolver final : public Solver {
+class SweepSolver final : public GroupSolver {
  public:
-  void prepare(hipStream_t s) override { load_code_dist(s); }
-  explicit SweepSolver(const DeviceGraph& g) : g_(g) {
+  explicit SweepSolver(const DeviceGraph& g) : GroupSolver(g) {
     const int64_t n = std::max<int64_t>(g.n, 1);
     dist_.alloc((size_t)n * sizeof(int32_t));
     fl_.alloc((size_t)n * sizeof(int32_t));
@@ -744,37 +716,9 @@ class SweepSolver final : public Solver {
     hctr_ = std::make_unique<PinnedBuf>(sizeof(Ctr));
   }
   void run(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
-           RunStats* st, hipStream_t s) override {
-    run_impl(K, qoff, qids, F, edges2, nullptr, nullptr, 0, st, s);
-  }
-  void run_dist(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int32_t* dist_dev,
-                int64_t ld, RunStats* st, hipStream_t s) override {
-    check_dist_out(g_, dist_dev, ld);
-    run_impl(K, qoff, qids, F, nullptr, dist_dev, nullptr, ld, st, s);
-  }
-  void run_parents(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F,
-                   int32_t* dist_dev, int32_t* parent_dev, int64_t ld, RunStats* st,
-                   hipStream_t s) override {
-    check_dist_out(g_, dist_dev, ld);
-    if (!parent_dev) fail("run_parents: no parent output");
-    run_impl(K, qoff, qids, F, nullptr, dist_dev, parent_dev, ld, st, s);
-  }
-  void run_profile(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* reach,
-                   int32_t* ecc, int64_t* hist, int64_t nbins, int64_t ld, RunStats* st,
-                   hipStream_t s) override {
-    ProfileScope scope{prof_};
-    prof_.begin(reach, ecc, hist, nbins, ld);
-    run_impl(K, qoff, qids, F, nullptr, nullptr, nullptr, 0, st, s);
-  }
-
- private:
-  void run_impl(int64_t K, const int64_t* qoff, const int32_t* qids, int64_t* F, int64_t* edges2,
-                int32_t* dout, int32_t* pout, int64_t ld, RunStats* st, hipStream_t s) {
-    const int32_t* n2o = pout ? inv_.get(g_, s) : nullptr;
+           const RunOutputs& out, RunStats* st, hipStream_t s) override {
+    begin_run(K, qoff, edges2, out, s);
     const int64_t n = g_.n;
-    int64_t maxs = 1;
-    for (int64_t k = 0; k < K; ++k) maxs = std::max(maxs, qoff[k + 1] - qoff[k]);
-    src_.ensure((size_t)maxs * sizeof(int32_t));
     for (int64_t k = 0; k < K; ++k) {
       const int64_t ns = qoff[k + 1] - qoff[k];
       MSBFS_HIP_CHECK(hipMemsetAsync(dist_.p, 0xFF, (size_t)std::max<int64_t>(n, 1) * 4, s));
@@ -811,16 +755,12 @@ class SweepSolver final : public Solver {
       MSBFS_HIP_CHECK(hipStreamSynchronize(s));
       F[k] = (int64_t)h[0];
       if (edges2) edges2[k] = (int64_t)h[1];
-      if (dout) gather_dist(g_, dist_.as<int32_t>(), dout + k * ld, s);
-      if (pout) parent_row(g_, dist_.as<int32_t>(), n2o, pout + k * ld, s);
-      prof_.row(dist_.as<int32_t>(), n, k, s);
+      group_outputs(dist_.as<int32_t>(), k, out, s);
     }
   }
 
-  const DeviceGraph& g_;
-  ProfileOut prof_;
-  DevBuf dist_, fl_, ctr_, red_, src_;
-  InverseMap inv_;
+ private:
+  DevBuf dist_, fl_, ctr_, red_;
   std::unique_ptr<PinnedBuf> hctr_;
 };
 

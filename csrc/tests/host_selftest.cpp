@@ -556,8 +556,8 @@ int main(int argc, char** argv) {
     const int64_t ld = l1.n + 3, K = q.K();
     std::vector<int32_t> d1((size_t)(K * ld), 77), d8((size_t)(K * ld), 77);
     std::vector<int64_t> Fd1, Fd8;
-    cpu_msbfs_all(l1, q, Fd1, nullptr, 1, d1.data(), ld);
-    cpu_msbfs_all(l1, q, Fd8, nullptr, T, d8.data(), ld);
+    cpu_msbfs_all(l1, q, Fd1, nullptr, 1, RunOutputs::distances(d1.data(), ld));
+    cpu_msbfs_all(l1, q, Fd8, nullptr, T, RunOutputs::distances(d8.data(), ld));
     CHECK(Fd1 == F1 && Fd8 == F1 && d1 == d8);
     bool ok = true;
     for (int64_t k = 0; k < K; ++k) {
@@ -572,11 +572,10 @@ int main(int argc, char** argv) {
     const int64_t nb = 3, pld = 5;
     std::vector<int64_t> r1((size_t)K), r8((size_t)K), h1((size_t)(K * pld), -5), h8 = h1, Fp1, Fp8;
     std::vector<int32_t> e1v((size_t)K), e8v((size_t)K);
-    CpuProfile p1, p8;
-    p1.reach = r1.data(), p1.ecc = e1v.data(), p1.hist = h1.data(), p1.nbins = nb, p1.ld = pld;
-    p8.reach = r8.data(), p8.ecc = e8v.data(), p8.hist = h8.data(), p8.nbins = nb, p8.ld = pld;
-    cpu_msbfs_all(l1, q, Fp1, nullptr, 1, nullptr, 0, nullptr, &p1);
-    cpu_msbfs_all(l1, q, Fp8, nullptr, T, nullptr, 0, nullptr, &p8);
+    const RunOutputs p1 = RunOutputs::profile(r1.data(), e1v.data(), h1.data(), nb, pld);
+    const RunOutputs p8 = RunOutputs::profile(r8.data(), e8v.data(), h8.data(), nb, pld);
+    cpu_msbfs_all(l1, q, Fp1, nullptr, 1, p1);
+    cpu_msbfs_all(l1, q, Fp8, nullptr, T, p8);
     CHECK(Fp1 == F1 && Fp8 == F1 && r1 == r8 && e1v == e8v && h1 == h8);
     ok = true;
     for (int64_t k = 0; k < K; ++k) {

@@ -49,7 +49,7 @@ void run_case(const HostCsr& g, const QuerySet& q, int nthreads, int64_t pad) {
   const int64_t K = q.K(), ld = g.n + pad;
   std::vector<int32_t> dist((size_t)(K * ld + 1), kSentinel), parent((size_t)(K * ld + 1), kSentinel);
   std::vector<int64_t> F, F2;
-  cpu_msbfs_all(g, q, F, nullptr, nthreads, dist.data(), ld, parent.data());
+  cpu_msbfs_all(g, q, F, nullptr, nthreads, RunOutputs::parents(dist.data(), parent.data(), ld));
   cpu_msbfs_all(g, q, F2, nullptr, 1);
   CHECK(F == F2);
   for (int64_t k = 0; k < K; ++k) {
@@ -61,7 +61,7 @@ void run_case(const HostCsr& g, const QuerySet& q, int nthreads, int64_t pad) {
   // a parent matrix alone is not a mode: the distance matrix may be left out, the parents not
   // computed from anything else
   std::vector<int32_t> p2((size_t)(K * ld + 1), kSentinel);
-  cpu_msbfs_all(g, q, F2, nullptr, nthreads, nullptr, ld, p2.data());
+  cpu_msbfs_all(g, q, F2, nullptr, nthreads, RunOutputs::parents(nullptr, p2.data(), ld));
   CHECK(p2 == parent);
 }
 
@@ -76,7 +76,7 @@ void discoverer_case() {
   q.add({0});
   std::vector<int32_t> dist(5), parent(5);
   std::vector<int64_t> F;
-  cpu_msbfs_all(g, q, F, nullptr, 1, dist.data(), 5, parent.data());
+  cpu_msbfs_all(g, q, F, nullptr, 1, RunOutputs::parents(dist.data(), parent.data(), 5));
   CHECK(g.col[g.rowptr[3]] == 2);  // 3's first row entry is 2; BFS from 0 discovers 3 from 1
   CHECK(parent[3] == 2 && parent[1] == 0 && parent[2] == 0 && parent[0] == 0 && parent[4] == -1);
   CHECK(dist[3] == 2 && dist[4] == -1 && F[0] == 4);

@@ -153,29 +153,38 @@ class Solver:
         >= n untouched). One solver pass of rows at a time is staged on the device.
         out_ptr: an integer device address of K x ld int32 (ld defaults to n) that receives the
         rows instead; nothing is copied to the host and BfsResult.dist is None."""
+        if out_ptr is not None and out is not None:
+            raise ValueError("give out_ptr (device) or out (host), not both")
+        return self._matrix_run("msbfs_solver_run_dist", queries,
+                                None if out_ptr is None else [out_ptr], 1, ld, stream, out)
+
+    def _matrix_run(self, fn: str, queries: QuerySet, ptrs, count: int, ld: Optional[int],
+                    stream: Optional[int], out: Optional[np.ndarray] = None) -> BfsResult:
+        """distances() / parents(): `count` K x ld int32 matrices through the entry point `fn`,
+        into the device addresses `ptrs`, or (ptrs None) through `fn`_host into host matrices
+        (the first one `out` when given), returned as their first n columns."""
         K = queries.K
         n = self.graph.n
         F = np.zeros(K, dtype=np.int64)
         st = native.Stats()
-        L = native.lib()
-        sp = C.c_void_p(stream) if stream else None
-        qo, qi = native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32)
-        if out_ptr is not None:
-            if out is not None:
-                raise ValueError("give out_ptr (device) or out (host), not both")
+        if ptrs is not None:
             ld = n if ld is None else int(ld)
             if ld < n:
                 raise ValueError("ld must be at least n")
-            if K:
-                native.check(L.msbfs_solver_run_dist(self._h, K, qo, qi, native.ptr(F, C.c_int64),
-                                                     C.c_void_p(int(out_ptr)), ld, C.byref(st), sp))
-            return BfsResult(F, None, st.as_dict(), None)
-        D, ld = _host_dist_out(K, n, out, ld)
+            args = [C.c_void_p(int(p)) for p in ptrs]
+            views = [None] * count
+        else:
+            D, ld = _host_dist_out(K, n, out, ld)
+            hosts = [D] + [np.full((K, ld), -1, dtype=np.int32) for _ in range(count - 1)]
+            args = [native.ptr(m, C.c_int32) for m in hosts]
+            views = [m[:, :n] for m in hosts]
+            fn += "_host"
         if K:
-            native.check(L.msbfs_solver_run_dist_host(self._h, K, qo, qi, native.ptr(F, C.c_int64),
-                                                      native.ptr(D, C.c_int32), ld, C.byref(st),
-                                                      sp))
-        return BfsResult(F, None, st.as_dict(), D[:, :n])
+            native.check(getattr(native.lib(), fn)(
+                self._h, K, native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32),
+                native.ptr(F, C.c_int64), *args, ld, C.byref(st),
+                C.c_void_p(stream) if stream else None))
+        return BfsResult(F, None, st.as_dict(), *views)
 
     def parents(self, queries: QuerySet, dist_ptr: Optional[int] = None,
                 parent_ptr: Optional[int] = None, ld: Optional[int] = None,
@@ -192,29 +201,9 @@ class Solver:
         without the other raises ValueError."""
         if (dist_ptr is None) != (parent_ptr is None):
             raise ValueError("give both dist_ptr and parent_ptr (device) or neither (host)")
-        K = queries.K
-        n = self.graph.n
-        F = np.zeros(K, dtype=np.int64)
-        st = native.Stats()
-        L = native.lib()
-        sp = C.c_void_p(stream) if stream else None
-        qo, qi = native.ptr(queries.off, C.c_int64), native.ptr(queries.ids, C.c_int32)
-        if dist_ptr is not None:
-            ld = n if ld is None else int(ld)
-            if ld < n:
-                raise ValueError("ld must be at least n")
-            if K:
-                native.check(L.msbfs_solver_run_parents(
-                    self._h, K, qo, qi, native.ptr(F, C.c_int64), C.c_void_p(int(dist_ptr)),
-                    C.c_void_p(int(parent_ptr)), ld, C.byref(st), sp))
-            return BfsResult(F, None, st.as_dict(), None, None)
-        D, ld = _host_dist_out(K, n, None, ld)
-        Pm = np.full((K, ld), -1, dtype=np.int32)
-        if K:
-            native.check(L.msbfs_solver_run_parents_host(
-                self._h, K, qo, qi, native.ptr(F, C.c_int64), native.ptr(D, C.c_int32),
-                native.ptr(Pm, C.c_int32), ld, C.byref(st), sp))
-        return BfsResult(F, None, st.as_dict(), D[:, :n], Pm[:, :n])
+        return self._matrix_run("msbfs_solver_run_parents", queries,
+                                None if dist_ptr is None else [dist_ptr, parent_ptr], 2, ld,
+                                stream)
 
     def profile(self, queries: QuerySet, bins=64, stream: Optional[int] = None) -> BfsResult:
         """F exactly as run() returns it plus each group's level profile, at the speed of run():
