@@ -81,10 +81,12 @@ struct Tuning {
   // of a plain F run's traversal and are counted through their parents. 0 off, 1 on wherever it
   // is legal, -1 (default) on where leaves are at least 1/8 of the non-isolated vertices
   int leaf = -1;
-  // test key: at most this many blocks (1..2048) for every grid-stride level kernel, so that one
-  // block of a small graph runs the hundreds of tiles at which the register counters spill and
-  // the LDS queues flush mid-loop (tests/test_block_loops_gpu.py). 0 (default): no cap, every
-  // grid as computed. Changes no decision and no count, only how many blocks share a level
+  // test key: at most this many blocks (1..2048) for every grid-stride level kernel, the tiled
+  // first pull level's k_pfx_tiles (one block per CU otherwise) included, so that one block of a
+  // small graph runs the hundreds of tiles at which the register counters spill and the LDS
+  // queues flush mid-loop (tests/test_block_loops_gpu.py, tests/test_prefix_level_gpu.py).
+  // 0 (default): no cap, every grid as computed. Changes no decision and no count, only how many
+  // blocks share a level
   int max_grid = 0;
   std::string dirs;    // forced per-level directions 'T'/'B' (tests, experiments)
 

@@ -215,7 +215,7 @@ int BitparSolver::tiles_pull(Loop& S, hipStream_t s, const uint64_t* R, uint64_t
   const int64_t nwords = (g_.n + 31) / 32;
   MSBFS_HIP_CHECK(hipMemsetAsync(fbm_tile_.p, 0, (size_t)nwords * sizeof(uint32_t), s));
   const uint32_t* pvis = snap ? snap : anyvis_.as<uint32_t>();
-  const int grid = std::max(1, num_cus());
+  const int grid = cap(std::max(1, num_cus()));  // (one block per CU; max_grid: fewer)
   // tile ranges: one launch for the whole level, or one per own-vertex range of a chunked
   // hybrid phase A (each range's rows are final once its launch and, for the first, the big
   // vertices' finalize ran; on_chunk then packs and sends them while the next range computes)

@@ -13,8 +13,9 @@ alone that the graphs are large enough for that.
 Pull kinds 'p', 't' and 'h' are taken from the graph's vertex count, isolated ids included
 (pull_plan.hpp), so test_capped_grid_prefix runs them on uniform graphs padded with isolated ids
 to 2^22 + 1 vertices (the big LDS hub bitmap, NarrowHubBig) and to 2^21 (the small one, NarrowHub:
-the hub_small cases). k_pfx_tiles itself has a grid of one block per CU that the key leaves alone;
-its reach is stated in test_gpu_kernels.py::test_bitpar_tiled_first_pull.
+the hub_small cases). The key caps k_pfx_tiles' grid (one block per CU otherwise) as well, but on
+these graphs a tile never gains a bit in every pass; its counter spills are the business of
+test_prefix_level_gpu.py::test_sun.
 
 What the records cannot show is said where it applies: whether k_td_fused walked the bitmap is
 inferred from the kernel's own condition (a level inside a batch, frontier >= td_bm), and the
@@ -308,7 +309,7 @@ def test_capped_grid_prefix(inputs, case, W, mg):
         assert all(r["kind"] == "h" for r in tr if r["dir"] == "B"), (what, tr)
     _assert_paths(name, tuning, tr, stats, core, what)
     if tiles is None:
-        return  # (k_pfx_tiles' own grid is not capped: no reach to show here)
+        return  # (k_pfx_tiles: the records hold no list it loops over; see test_prefix_level_gpu.py)
     deg = np.diff(core.rowptr)
     wide = dict(wide_first=int((deg >= bl.WIDE_DEFAULT).sum()), wide_later=int((deg >= 1024).sum()))
     print(what, [(r["level"], r["dir"] + r["kind"], t)

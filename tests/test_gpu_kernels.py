@@ -359,9 +359,10 @@ def test_bitpar_tiled_first_pull(msbfs_pkg, K):
             # after the level went through a pass (128 / words vertices each) unless it is one of
             # the big vertices (more than 1024 prefix entries: fewer than nnz / 1024); the grid
             # is one block of 16 waves per CU.
-            # Open gap: at 4 words (the tiles4 runs, tiles_w = 4) a pass takes 32 vertices but a
-            # tile holds fewer, and this bound gives only ~27 passes per wave on this graph. So
-            # nothing here shows that the D = 5 spill of k_pfx_tiles<4> runs: it is unproven.
+            # At 4 words (the tiles4 runs, tiles_w = 4) a pass takes 32 vertices but a tile holds
+            # fewer, and this bound gives only ~27 passes per wave on this graph: the D = 5
+            # spill of k_pfx_tiles<4> (and of 8 and 16 words, with full counters) is reached in
+            # test_prefix_level_gpu.py::test_sun, whose grid is capped by max_grid.
             import torch
             waves = 16 * torch.cuda.get_device_properties(0).multi_processor_count
             passes = (tr[1]["active"] - g.nnz // 1024) / (128 // words) / waves
